@@ -18,8 +18,15 @@ Workloads (BASELINE.json configs):
     one gradient all-reduce per step, the whole DP step replayed as one HIP graph.  The line
     also carries `weak` (4096 rows per rank, same semantics).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  Everything else --
+the dominant-kernel roofline and per-kernel times, the secondary workloads named above (configs3_n1,
+projection_w8, weak, configs0 / head_net / configs2 / configs4_projection_w8, dropin_loop) and the CPU
+baseline -- is measured only with --full.  --dump-outputs DIR writes what the last timed step computed
+(loss, Q values, TD terms, sampled indices, online and target parameters) as DIR/<name>.npy; the inputs
+are seeded, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0 (fields: see the driver contract in DESIGN.md section 5).
 """
@@ -46,6 +53,9 @@ from dqn.engine import LearnEngine, hybrid_spec, mlp_spec  # noqa: E402
 PEAK_FP32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: F32 matrix, dense
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: BF16 MFMA ~2.5 PF dense (no sparsity)
 PEAK_HBM_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+
+
+DUMP_MAX_ELEMS = 2_000_000       # per dumped array (8 MB of float32): six arrays stay well under 64 MB
 
 
 def log(*a):
@@ -109,6 +119,15 @@ def parse():
     p.add_argument("--per-numpy121", action="store_true",
                    help="PER: the SumTree arithmetic of the reference's pinned numpy 1.21 (float32 change and "
                         "ancestor sums in update order, k_per_chain) instead of numpy >= 2's float64")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline figure: the dominant-kernel roofline and "
+                        "per-kernel times, the secondary workloads (configs3_n1 / projection_w8 / weak, configs0, "
+                        "head_net, configs2, configs4_projection_w8, dropin_loop) and the CPU baseline; the "
+                        "--no-kernel-timing / --no-extras / --no-cpu-baseline switches take single parts out again")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (loss, q, td, batch_idx, "
+                        "online_params, target_params) as DIR/<name>.npy (float32 / float64; arrays past "
+                        f"{DUMP_MAX_ELEMS} elements as a fixed seeded sample)")
     a = p.parse_args()
     if a.capacity is None:
         a.capacity = 100_000 if a.net == "hybrid84" else 1_000_000
@@ -361,9 +380,32 @@ def timed_steps(step, steps, dist, device, chain=1):
     return el
 
 
-def run_learner(args, eng, world, backend, steps, warmup, dist, device, dp=None):
+def dump_outputs(eng, out_dir):
+    """What a caller of the learn step receives after it, as out_dir/<name>.npy: the loss, the three
+    Q-value blocks and TD terms of the minibatch, the sampled indices (both slots of the double-buffered
+    draw), and the online and target parameter vectors.  Integers are written as float64 (exact), the
+    rest as float32; an array past DUMP_MAX_ELEMS elements is cut to a fixed seeded sample of its entries."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {
+        "loss": np.array([eng.loss()], dtype=np.float64),
+        "q": eng.q.detach().cpu().numpy().astype(np.float32),
+        "td": eng.td.detach().cpu().numpy().astype(np.float32),
+        "batch_idx": eng.batch_idx_slots.detach().cpu().numpy().astype(np.float64),
+        "online_params": eng.params[:eng.n_params].detach().cpu().numpy().astype(np.float32),
+        "target_params": eng.target_params[:eng.n_params].detach().cpu().numpy().astype(np.float32),
+    }
+    for name, a in arrays.items():
+        if a.size > DUMP_MAX_ELEMS:
+            pick = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+def run_learner(args, eng, world, backend, steps, warmup, dist, device, dp=None, after_timed=None):
     """Warm up, then time `steps` learn steps (single GPU: the engine's graph; DP: the whole DP
-    step as one HIP graph over RCCL).  Returns (seconds, dp_graph)."""
+    step as one HIP graph over RCCL).  after_timed(eng), if given, runs right after the timed steps
+    (stream idle), before the minibatch drawn ahead is consumed.  Returns (seconds, dp_graph)."""
     # conv nets exchange per-layer gradient buckets on a side stream, overlapped with the rest of
     # the backward (dp_learn_step_bucketed); the MLP's 428 KB gradient stays one all-reduce
     dp = world > 1 if dp is None else dp   # the data-parallel step (DQNX_BENCH_FORCE_DP: also at world 1)
@@ -412,6 +454,8 @@ def run_learner(args, eng, world, backend, steps, warmup, dist, device, dp=None)
                 eager_step()
         chain = gs
     el = timed_steps(step, steps, dist, device, chain)
+    if after_timed is not None:
+        after_timed(eng)
     if prefetch and (dp or chain == 1):   # consume the minibatch drawn ahead (none pending after)
         if dp and bucketed:
             dp_learn_step_bucketed(eng, soft_update=True)
@@ -1080,7 +1124,9 @@ def main():
     Bl = Bg // world
     local = dpmode and args.local_sampling and not per
     eng = make_engine(args, spec, Bg, world, rank, device, local=local)
-    el, dp_graph = run_learner(args, eng, world, backend, args.steps, args.warmup, dist, device, dp=dpmode)
+    dump = (lambda e: dump_outputs(e, args.dump_outputs)) if args.dump_outputs and rank == 0 else None
+    el, dp_graph = run_learner(args, eng, world, backend, args.steps, args.warmup, dist, device, dp=dpmode,
+                               after_timed=dump)
     loss = eng.loss()
     ms_per_step = el / args.steps * 1e3
     value = Bg * args.steps / el
@@ -1088,7 +1134,7 @@ def main():
     # ---- dominant-kernel roofline: HIP-event-timed graph steps with / without each kernel ----
     roofline = None
     kernels = []
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         flags = C.STEP_GRADS_ONLY if dpmode else C.STEP_SOFT_UPDATE
         if args.prefetch and not per:   # the plan the timed loop ran (steady state: no sampler launch)
             flags |= C.STEP_PREFETCH
@@ -1096,7 +1142,7 @@ def main():
         kernels, roofline = dominant_roofline(args, eng, flags, Bl, f"{args.net}_b{Bl}{tag}")
 
     extras = {}
-    if not args.no_extras and args.net == "mlp" and not per and args.compute == "fp32":
+    if args.full and not args.no_extras and args.net == "mlp" and not per and args.compute == "fp32":
         del eng
         torch.cuda.empty_cache()
         if not dpmode:
@@ -1116,7 +1162,7 @@ def main():
             del weng
 
     cpu = None
-    if rank == 0 and not dpmode and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not dpmode and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args, Bg)
         except Exception as ex:  # the baseline must never hide the GPU number
@@ -1130,6 +1176,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": scaling,

@@ -92,6 +92,22 @@ def state_array(st):
 
 
 # ---------------------------------------------------------------------------------------
+MAX_FILE_BYTES = 1 << 20   # no committed file is larger than 1 MiB
+
+
+def save_fixture(fn, out):
+    """One compressed npz; a fixture that would pass MAX_FILE_BYTES keeps its Adam moments (m_<i>, v_<i>)
+    in a second archive `<fn>.part2` (tests/golden_io.py load_fixture reads both)."""
+    np.savez_compressed(fn, **out)
+    if os.path.getsize(fn) <= MAX_FILE_BYTES:
+        return
+    moments = {k: a for k, a in out.items() if k.split("_")[0] in ("m", "v") and k.split("_")[1].isdigit()}
+    np.savez_compressed(fn, **{k: a for k, a in out.items() if k not in moments})
+    with open(fn + ".part2", "wb") as f:   # (a file object: savez would append ".npz" to the name)
+        np.savez_compressed(f, **moments)
+    assert max(os.path.getsize(fn), os.path.getsize(fn + ".part2")) <= MAX_FILE_BYTES, fn
+
+
 def gen_sampler(replay_mod):
     """ReplayMemoryNaive.sample_transitions (R:dqn/replay_memory.py:38-39) index vectors."""
     cases = []
@@ -250,7 +266,7 @@ def gen_learn(agent_mod, nn_conf_func, tag, spec_fn, obs_dim, batch, buffer, n_f
                     out[f"{nm}_{i}"] = t[::stride]
                 out[f"{nm}_sum_{i}"] = np.float64(t.astype(np.float64).sum())
         fn = os.path.join(HERE, f"learn_{tag}_{algo}.npz")
-        np.savez_compressed(fn, **out)
+        save_fixture(fn, out)
         print(os.path.basename(fn), os.path.getsize(fn), "bytes; losses", rec["loss"])
 
 

@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """`.pack` checkpoint interop in both directions against the REFERENCE's own Network.save / load
 (R:dqn/network.py:27-47, through its msgpack-numpy hooks R:dqn/utils/msgpack_numpy.py:74-130).
-Build container only: the reference is imported read-only with make_golden.py's recipe
-(SURVEY.md §8(c)); nothing of it is copied.  tests/test_pack_interop.py drives the three roles in
-separate processes, because the drop-in package and the reference are both named `dqn`:
+Needs a checkout of the reference: it is imported read-only with make_golden.py's recipe
+(SURVEY.md §8(c)); nothing of it is copied.  The three roles run in separate processes, because
+the drop-in package and the reference are both named `dqn`:
 
     pack_interop.py ours-save DIR   drop-in networks (dqn.network) -> DIR/ours_<case>.pack + .npz
     pack_interop.py ref         DIR   reference networks .load(ours_<case>.pack), compare bit for bit;
                                       then the reference saves DIR/ref_<case>.pack + .npz
     pack_interop.py ours-load DIR   drop-in networks .load(ref_<case>.pack), compare bit for bit
+    pack_interop.py golden    DIR   all three, then store the reference-written packs and their
+                                      tensor digests beside this file: the fixtures that
+                                      tests/test_pack_interop.py checks without the reference
 
 Cases: the MLP of R:env/custom_env/macro with lane/dqn_config.py:58-104 at D = 284 (dueling head)
 and D = 14 (linear head), and the HEAD TwoStreamHybridNetwork of R:env/dqn_config.py:148-193
@@ -90,9 +93,45 @@ def ref(out):
         print(f"ok ref-save {case}", flush=True)
 
 
+PART_BYTES = 900_000   # a committed file stays under 1 MiB: larger packs are stored in parts
+
+
+def golden(out):
+    """Run the three roles in DIR (one process each), then store what the reference wrote as the
+    fixtures of tests/test_pack_interop.py: ref_<case>.pack (in parts of PART_BYTES when larger) and
+    pack_interop.json (the cases, the reference-side metadata, shape and sha256 of every tensor the
+    reference saved)."""
+    import hashlib
+    import json
+    import subprocess
+    for role in ("ours-save", "ref", "ours-load"):
+        subprocess.run([sys.executable, os.path.abspath(__file__), role, out], check=True, cwd=out)
+    rec = {"meta": [float(m) if isinstance(m, float) else int(m) for m in META["ref"]], "cases": []}
+    for case, d, head, kind in CASES:
+        blob = open(os.path.join(out, f"ref_{case}.pack"), "rb").read()
+        parts = [blob[i:i + PART_BYTES] for i in range(0, len(blob), PART_BYTES)]
+        names = [f"ref_{case}.pack"] if len(parts) == 1 else [f"ref_{case}.pack.part{i}" for i in range(len(parts))]
+        for name, part in zip(names, parts):
+            with open(os.path.join(HERE, name), "wb") as f:
+                f.write(part)
+        want = np.load(os.path.join(out, f"ref_{case}.npz"))
+        rec["cases"].append({
+            "case": case, "obs_dim": d, "head": head, "kind": kind, "files": names,
+            "sha256": hashlib.sha256(blob).hexdigest(),
+            "tensors": {k: {"shape": list(want[k].shape),
+                            "sha256": hashlib.sha256(np.ascontiguousarray(want[k]).tobytes()).hexdigest()}
+                        for k in want.files}})
+    with open(os.path.join(HERE, "pack_interop.json"), "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print("ok golden", flush=True)
+
+
 if __name__ == "__main__":
     role, out = sys.argv[1], sys.argv[2]
     if role == "ref":
         ref(out)
+    elif role == "golden":
+        golden(out)
     else:
         ours(role, out)

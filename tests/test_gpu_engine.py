@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from golden_io import load_fixture
 from oracle import ref as O
 from parity import COMPARISONS, assert_grad_close, record_exemptions
 
@@ -392,7 +393,7 @@ def test_gpu_learn_golden(golden):
     Covers configs[1]'s batch (1024), configs[3]'s global batch (4096) and configs[4]'s PER
     batch (8192, fp32 arithmetic)."""
     E = _engine_mod()
-    z = np.load(os.path.join(GOLDEN, golden + ".npz"))
+    z = load_fixture(os.path.join(GOLDEN, golden + ".npz"))
     algo = str(z["algo"])
     per = algo.startswith("Per")
     obs_dim, batch, cap = int(z["obs_dim"]), int(z["batch"]), int(z["buffer"])

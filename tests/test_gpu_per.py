@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from golden_io import load_fixture
 from oracle import ref as O
 from parity import assert_grad_close
 
@@ -175,7 +176,7 @@ def test_gpu_per_learn_matches_oracle(obs_dim, batch, cap, n_fill, seed):
 
 def test_gpu_per_learn_golden():
     """Against the reference's own PER steps (tests/golden, made by make_golden.py)."""
-    z = np.load(os.path.join(GOLDEN, "learn_mlp284_PerDuelingDoubleDQNAgent.npz"))
+    z = load_fixture(os.path.join(GOLDEN, "learn_mlp284_PerDuelingDoubleDQNAgent.npz"))
     obs_dim, batch, cap = int(z["obs_dim"]), int(z["batch"]), int(z["buffer"])
     init = O.reference_init(O.mlp_spec(obs_dim, 8, "dueling"), int(z["seed"]))
     eng = per_engine(obs_dim, batch, cap)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from golden_io import load_fixture
 from oracle import ref as O
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -114,7 +115,7 @@ GOLDEN_LEARN = sorted(glob.glob(os.path.join(GOLDEN, "learn_*.npz")))
 
 @pytest.mark.parametrize("path", GOLDEN_LEARN, ids=[os.path.basename(p)[6:-4] for p in GOLDEN_LEARN])
 def test_oracle_learn_golden(path):
-    z = np.load(path)
+    z = load_fixture(path)
     L, recs = run_oracle_from_fixture(z)
     for s, r in enumerate(recs):
         assert np.array_equal(r.positions, z["pos"][s]), f"step {s} indices"

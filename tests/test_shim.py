@@ -10,7 +10,9 @@ from dqn.utils import pack
 from oracle import ref as O
 from refnets import Box, agent_kwargs, mlp_network_config
 
-REF_PACK = "/root/reference/env/custom_env/macro with lane/DuelingDoubleDQNAgent_lr0.0001_model_2e6_1e6.pack"
+# the reference's trained macro-lane checkpoint (R:env/custom_env/macro with lane/), stored as a fixture
+REF_PACK = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                        "DuelingDoubleDQNAgent_lr0.0001_model_2e6_1e6.pack")
 
 
 @pytest.mark.parametrize("cls,head", [(Networks.DuelingDeepQNetwork, "dueling"), (Networks.DeepQNetwork, "linear")])
@@ -37,7 +39,6 @@ def test_pack_roundtrip(tmp_path):
         assert torch.equal(v, net2.state_dict()[k])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PACK), reason="reference checkpoint not present")
 def test_loads_reference_checkpoint():
     """A .pack written by the reference's Network.save loads into the drop-in network."""
     params, step, eps, rew, ln = pack.load_pack(REF_PACK)

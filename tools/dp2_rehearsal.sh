@@ -12,7 +12,7 @@ for extra in "" "--algo PerDuelingDoubleDQNAgent --compute bf16 --global-batch 8
   tag=$([ -z "$extra" ] && echo mlp || echo c5)
   DQNX_SINGLE_DEVICE=1 DQNX_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 \
       --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 2962${#tag} \
-      bench.py --gpus 2 --steps ${STEPS:-100} --warmup 10 $extra > $OUT/bench_w2_$tag.json 2> $OUT/bench_w2_$tag.err \
+      bench.py --gpus 2 --steps ${STEPS:-100} --warmup 10 --full $extra > $OUT/bench_w2_$tag.json 2> $OUT/bench_w2_$tag.err \
       || { tail -20 $OUT/bench_w2_$tag.err; exit 1; }
   tail -c 1500 $OUT/bench_w2_$tag.json
 done

@@ -20,7 +20,7 @@ for W in "$@"; do
   python tools/pmc_traffic.py gpurun_out/pmc $P/pmc_traffic_$W.json > /dev/null || exit $?
   rm -rf gpurun_out/pmc gpurun_out/r06prof_$W
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r06prof_$W -o run -- \
-      python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extras $ARGS > $P/prof_bench_$W.json 2> $P/prof_bench_$W.err || exit $?
+      python3 bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --no-extras $ARGS > $P/prof_bench_$W.json 2> $P/prof_bench_$W.err || exit $?
   STATS=$(find gpurun_out/r06prof_$W -name "*kernel_stats.csv" | head -1)
   cp "$STATS" $P/kernel_stats_$W.csv || exit 1
   rm -rf gpurun_out/r06prof_$W

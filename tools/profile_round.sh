@@ -20,14 +20,14 @@ python tools/pmc_traffic.py gpurun_out/pmc $P/pmc_traffic_$NAME.json > /dev/null
 cp $P/pmc_traffic_$NAME.json profiles/pmc_traffic_$NAME.json
 rm -rf gpurun_out/pmc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- \
-    python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-extras ${BENCH_ARGS:-} > $OUT/prof_bench.json 2> $OUT/prof_bench.err || exit $?
+    python bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --no-extras ${BENCH_ARGS:-} > $OUT/prof_bench.json 2> $OUT/prof_bench.err || exit $?
 STATS=$(find $OUT/prof -name "*kernel_stats.csv" | head -1)
 cp "$STATS" $P/kernel_stats_$NAME.csv
 PMC_GROUPS=tools/pmc_groups_mfma.txt bash tools/pmc.sh || exit $?
 python tools/mfma_util.py gpurun_out/pmc $P/mfma_util_$NAME.json $P/kernel_stats_$NAME.csv > /dev/null || exit $?
 rm -rf gpurun_out/pmc
 if [ -z "${NO_BENCH:-}" ]; then
-  timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > $P/bench_$NAME.json 2> $OUT/bench.err || exit $?
+  timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > $P/bench_$NAME.json 2> $OUT/bench.err || exit $?
   cat $P/bench_$NAME.json
 fi
 echo "done $NAME"

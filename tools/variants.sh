@@ -10,7 +10,7 @@ mkdir -p $OUT
 while read -r name envs; do
   [ -z "$name" ] && continue
   case "$name" in \#*) continue ;; esac
-  env $envs timeout -k 10 150 python bench.py --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline --no-extras \
+  env $envs timeout -k 10 150 python bench.py --steps ${STEPS:-200} --warmup 20 --full --no-cpu-baseline --no-extras \
       ${BENCH_ARGS:-} > $OUT/$name.json 2> $OUT/$name.err || { echo "FAILED $name rc=$?" >> $OUT/summary.txt; exit 1; }
   python - "$name" "$OUT/$name.json" >> $OUT/summary.txt <<'EOF'
 import json, sys
