@@ -342,11 +342,17 @@ int dqnx_hard_update(dqnx_engine* e, void* stream);
  * 16-byte aligned device buffer of scratch_bytes >= dqnx_act_scratch_bytes(net, n) bytes (a
  * multiple of 4), zero-filled before its first use; every call leaves it ready for the next, so
  * calls with any n up to its size may share it on one stream.  MLP nets: one launch.  Two-stream
- * nets (TwoStreamHybridNetwork, R:env/dqn_config.py:66-143): one launch per conv layer, then the
- * dense stream + head as for an MLP on cat(flatten(conv), macro).  Stream-ordered, no sync. */
+ * nets (TwoStreamHybridNetwork, R:env/dqn_config.py:66-143): one launch for the whole conv stack
+ * where that is the faster call (two or more convs whose first layers fit a workgroup's LDS, and
+ * n <= 2 by default: DQNX_ACT_TS=2 takes it up to n = 256, DQNX_ACT_TS=0 never), else one launch
+ * per conv layer; then the dense stream + head as for an MLP on cat(flatten(conv), macro).
+ * dqnx_act_kernel_count reports the launches.  Stream-ordered, no sync. */
 uint64_t dqnx_act_scratch_bytes(const dqnx_net_desc* net, int32_t n);
 int dqnx_act(const dqnx_net_desc* net, const float* params, const float* obs, int32_t n, int32_t* actions,
              float* values, void* scratch, uint64_t scratch_bytes, void* stream);
+/* launches dqnx_act makes for n rows of this net (host only, no GPU);
+ * DQNX_EUNSUPPORTED where dqnx_act refuses the net */
+int dqnx_act_kernel_count(const dqnx_net_desc* net, int32_t n, int32_t* count);
 
 /* ---- drop-in Agent fast path: one host call per agent method (R:train.py:88-108) ---------------
  * dqnx_agent_stage_rng: Agent.learn()'s draw source -- snapshot `state625` (the caller's
@@ -365,7 +371,9 @@ int dqnx_act(const dqnx_net_desc* net, const float* params, const float* obs, in
  * dqnx_act_host: dqnx_act with HOST obs [n][obs_dim] and HOST actions [n]: the obs through pinned
  *   memory into the END of `scratch` (dqnx_act_host_scratch_bytes(net, n) bytes, zero-filled before
  *   its first use), one launch sequence, the actions back; synchronises `stream` (Network.actions,
- *   R:dqn/network.py:67-74, 110-117). */
+ *   R:dqn/network.py:67-74, 110-117).  MLP nets, and two-stream nets on the one-launch conv stack
+ *   with n rows in one row group (n <= 4, and where dqnx_act takes that stack): the kernels read the pinned obs and write the pinned
+ *   actions in place, with no copy calls, and the call waits on a completion word instead. */
 int dqnx_agent_stage_rng(dqnx_engine* e, int32_t which, const uint32_t* state625, int64_t* words);
 int dqnx_agent_launch(dqnx_engine* e, int32_t flags, void* stream);
 /* dqnx_agent_learn_mt: Agent.learn() on the caller's LIVE generator, uniform replay: `mt` = its 624
@@ -384,7 +392,8 @@ int dqnx_agent_readback(dqnx_engine* e, int32_t wait, dqnx_ctrl* out);
  *   calls it, with the GIL released, before a dqnx_agent_learn_mt (GIL held) whose previous readback
  *   is still unread, so no other Python thread is blocked for the length of a GPU wait. */
 int dqnx_agent_quiesce(dqnx_engine* e);
-/* dqnx_agent_choose: Agent.choose_actions(obses) (R:dqn/agent.py:92-99) in ONE call, MLP nets on the
+/* dqnx_agent_choose: Agent.choose_actions(obses) (R:dqn/agent.py:92-99) in ONE call, for every net
+ *   dqnx_act supports (MLP and two-stream), on the
  *   engine's online parameters: the greedy actions of the n HOST rows at obs_host (dqnx_act_host's
  *   launch: the advantage stream for dueling nets, R:dqn/network.py:110-117), and -- while the acting
  *   kernel runs -- for every env i in order: u = random.random() from the caller's LIVE MT19937 (mt =

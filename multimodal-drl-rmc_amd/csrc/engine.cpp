@@ -3863,8 +3863,9 @@ int dqnx_hard_update(dqnx_engine* e, void* stream) {
     return DQNX_OK;
 }
 
-// acting kernel geometry of a network (host only).  A two-stream net acts as its convs (one
-// launch each, act_hybrid.hip) followed by the MLP acting kernel on F = cat(flatten(conv), macro).
+// acting kernel geometry of a network (host only).  A two-stream net acts as its convs (one launch
+// for the whole stack where act_ts_plan applies, else one each; act_hybrid.hip) followed by the MLP
+// acting kernel on F = cat(flatten(conv), macro).
 static int act_plan_build(const dqnx_net_desc* net, NetPlan& np, ActArgs& a);
 
 // act_plan for the acting path's every call (choose_actions: one per env step): the plans of the last
@@ -3931,11 +3932,55 @@ static int act_plan_build(const dqnx_net_desc* net, NetPlan& np, ActArgs& a) {
     return DQNX_OK;
 }
 
-// two-stream scratch: conv outputs of every conv but the last, F [n][D]; the MLP part follows
+// The one-launch conv stack (act_hybrid.hip, k_act_conv_stack) applies: NC >= 2 convs, the redundant part
+// (micro grid, outputs of convs 1 .. NC-2, the weights a workgroup uses) fits LDS, at most kActTsMaxRows
+// rows (the shares are G x the last conv's output per row: the cap bounds the scratch; larger calls are
+// throughput-bound and keep the per-conv grids), and -- unless `any_route` -- the route knob says so:
+// DQNX_ACT_TS = 0 never, 2 wherever it applies, 1 (default) up to kActTsAutoRows rows, where the call
+// measured faster than with the per-conv launches (DQNX_ACT_TS_ROWS moves that threshold).
+// Fills the geometry, G and the LDS plan of `sa`.
+constexpr int kActTsMaxRows = 256;
+constexpr int kActTsAutoRows = 2;
+static bool act_ts_plan(const NetPlan& np, int n, ActStackArgs& sa, bool any_route = false) {
+    const int NC = (int)np.conv.size();
+    if (NC < 2 || NC > DQNX_MAX_CONV || n > kActTsMaxRows) return false;
+    if (!any_route) {
+        const int mode = route_knob("DQNX_ACT_TS", 1);
+        if (mode == 0 || (mode == 1 && n > route_knob("DQNX_ACT_TS_ROWS", kActTsAutoRows))) return false;
+    }
+    memset(&sa, 0, sizeof(sa));
+    sa.NC = NC;
+    for (int l = 0; l < NC; l++) {
+        const ConvPlan& cp = np.conv[l];
+        ActConvGeom& q = sa.L[l];
+        q.Ci = cp.Ci; q.Hi = cp.Hi; q.Wi = cp.Wi; q.Co = cp.Co; q.Ho = cp.Ho; q.Wo = cp.Wo;
+        q.kh = cp.kh; q.kw = cp.kw; q.sh = cp.sh; q.sw = cp.sw; q.ph = cp.ph; q.pw = cp.pw;
+        q.off = cp.off;
+    }
+    // workgroups conv NC-1's channels are split over: 32 for one or two rows (the latency-bound agent call),
+    // 16 for more (measured; DQNX_ACT_TS_G overrides), the largest divisor of Co at or below it
+    int G = std::max(1, std::min(route_knob("DQNX_ACT_TS_G", n <= 2 ? 32 : 16), np.conv[NC - 2].Co));
+    while (np.conv[NC - 2].Co % G) G--;
+    sa.G = G;
+    const size_t lds = act_stack_plan(sa);
+    return lds > 0 && lds <= kActMaxLds;
+}
+
+// two-stream scratch: the per-conv launches' conv outputs of every conv but the last, or the one-launch
+// stack's shares [n][G][Co Ho Wo of the last conv]; then F [n][D]; the MLP part follows.  Sized for
+// whichever route needs more (the route is chosen per call), and never less than a smaller n needs.
 static uint64_t act_conv_scratch_bytes(const NetPlan& np, int n, int D) {
     uint64_t b = 0;
     for (size_t l = 0; l + 1 < np.conv.size(); l++)
         b += (uint64_t)n * np.conv[l].Co * np.conv[l].Ho * np.conv[l].Wo * 4;
+    ActStackArgs sa;
+    const int nt = std::min(n, kActTsMaxRows);
+    for (int m : {std::min(nt, 2), nt}) {   // (G is larger for n <= 2: a scratch for n rows serves those calls too)
+        if (m <= 0 || !act_ts_plan(np, m, sa, true)) continue;
+        const ConvPlan& cl = np.conv.back();
+        b = std::max(b, (uint64_t)m * sa.G * cl.Co * cl.Ho * cl.Wo * 4);
+    }
+    b = (b + 15) / 16 * 16;
     b += (uint64_t)n * D * 4;
     return (b + 255) / 256 * 256;
 }
@@ -3948,6 +3993,32 @@ uint64_t dqnx_act_scratch_bytes(const dqnx_net_desc* net, int32_t n) {
     const uint64_t mlp = act_scratch_bytes(n, a.out[0], a.ld, a.L, a.L >= 2 ? a.out[1] : 0);
     if (!mlp) return 0;
     return (net->kind == DQNX_NET_MLP ? 0 : act_conv_scratch_bytes(np, n, a.D)) + mlp;
+}
+
+int dqnx_act_kernel_count(const dqnx_net_desc* net, int32_t n, int32_t* count) {
+    if (!net || !count || n < 0) return set_error(DQNX_EINVAL, "dqnx_act_kernel_count: bad argument");
+    const NetPlan* npp = nullptr;
+    ActArgs a;
+    const int rc = act_plan(net, &npp, a);
+    if (rc) return rc;
+    if (act_rows_per_block(std::max(n, 1), a.ld) == 0)
+        return set_error(DQNX_EUNSUPPORTED, "dqnx_act: layer width %d does not fit LDS", a.ld);
+    ActStackArgs sa;
+    if (net->kind == DQNX_NET_MLP) *count = 1;
+    else *count = (act_ts_plan(*npp, n, sa) ? 1 : (int32_t)npp->conv.size()) + 1;
+    return DQNX_OK;
+}
+
+// the dqnx_act_host call reads the obs from and writes the actions to its pinned block in place (no copy
+// calls) and polls a completion word: MLP nets, and two-stream nets on the one-launch conv stack with one
+// row group (several row groups would each re-read their rows over the host link G times, and store no word)
+static bool act_host_direct(const dqnx_net_desc* net, int32_t n) {
+    if (net->kind == DQNX_NET_MLP) return true;
+    const NetPlan* npp = nullptr;
+    ActArgs a;
+    ActStackArgs sa;
+    if (net->kind != DQNX_NET_TWO_STREAM || act_plan(net, &npp, a)) return false;
+    return n <= act_rows_per_block(n, a.ld) && act_ts_plan(*npp, n, sa);
 }
 
 // done_flag: the MLP acting kernel stores done_seq there (system scope) after the actions (dqnx_act_host)
@@ -3976,7 +4047,11 @@ static int act_impl(const dqnx_net_desc* net, const float* params, const float* 
     a.params = params; a.obs = obs; a.actions = actions; a.values = values; a.n = n;
     // the acting kernels store the completion word from row group 0 only when the launch has ONE row
     // group (n <= R rows per workgroup: R halves for inputs wider than 2048 / 4096 floats)
-    a.done_flag = (net->kind == DQNX_NET_MLP && n <= R) ? done_flag : nullptr;
+    // A two-stream net's MLP kernel runs last: it signals where the conv stack is one launch (the route
+    // dqnx_act_host reads the obs in place for, act_host_direct)
+    ActStackArgs sa;
+    const bool ts = net->kind == DQNX_NET_TWO_STREAM && n > 0 && act_ts_plan(np, n, sa);
+    a.done_flag = ((net->kind == DQNX_NET_MLP || ts) && n <= R) ? done_flag : nullptr;
     if (signals) *signals = a.done_flag != nullptr && n > 0;
     a.done_seq = done_seq;
     if (n == 0) return DQNX_OK;
@@ -3993,12 +4068,21 @@ static int act_impl(const dqnx_net_desc* net, const float* params, const float* 
         int in_off = np.macro_len;   // the micro grid viewed as (c, h, w) (R:env/dqn_config.py:126-128)
         char* cur = sc;
         float* F = nullptr;
-        {
+        if (ts) {   // one launch: shares at the start, F after them, the MLP kernel's ticket words at the END
+            const ConvPlan& cl = np.conv.back();
+            const uint64_t shb = ((uint64_t)n * sa.G * cl.Co * cl.Ho * cl.Wo * 4 + 15) / 16 * 16;
+            F = (float*)(sc + shb);
+            sa.params = params; sa.in = obs; sa.in_stride = in_stride; sa.in_off = in_off; sa.macro_len = np.macro_len;
+            sa.F = F; sa.F_stride = a.D; sa.shares = (float*)sc; sa.n = n; sa.R = R;
+            sa.tickets = (uint32_t*)(sc + scratch_bytes) - 1;
+            rc = launch_act_conv_stack(sa, s);
+            if (rc) return rc;
+        } else {
             uint64_t b = 0;
             for (int l = 0; l + 1 < NC; l++) b += (uint64_t)n * np.conv[l].Co * np.conv[l].Ho * np.conv[l].Wo * 4;
             F = (float*)(sc + b);
         }
-        for (int l = 0; l < NC; l++) {
+        for (int l = 0; !ts && l < NC; l++) {   // one launch per conv
             const ConvPlan& cp = np.conv[l];
             ActConvArgs ca;
             memset(&ca, 0, sizeof(ca));
@@ -4264,9 +4348,10 @@ static int act_host_launch(const dqnx_net_desc* net, const float* params, const 
     c.s = s;
     c.pa = (int32_t*)(pin + (size_t)n * net->obs_dim * 4);
     memcpy(pin, obs_host, (size_t)n * net->obs_dim * 4);
-    if (net->kind == DQNX_NET_MLP) {
-        // one launch: the acting kernel reads the obs from and writes the actions to the pinned,
-        // fine-grained block in place (no copy calls) and then a completion word, which the host
+    if (act_host_direct(net, n)) {
+        // the acting kernels (one for an MLP; the conv stack, then the MLP kernel for a two-stream
+        // net) read the obs from and write the actions to the pinned, fine-grained block in place
+        // (no copy calls) and then a completion word, which the host
         // polls instead of synchronising the stream (the wake-up of a stream synchronisation costs
         // more than the kernel); a kernel that never signals ends the poll after ~0.5 s, and the
         // stream synchronisation then reports its error

@@ -811,6 +811,24 @@ struct ActConvArgs {
 };
 size_t act_conv_lds_bytes(const ActConvArgs& a);
 int launch_act_conv(const ActConvArgs& a, hipStream_t s);
+// two-stream acting, the whole conv stack (NC >= 2 convs) in one launch (act_hybrid.hip, k_act_conv_stack)
+struct ActConvGeom {
+    int Ci, Hi, Wi, Co, Ho, Wo, kh, kw, sh, sw, ph, pw;
+    int64_t off;   // weight [Co][Ci][kh][kw] in params; the bias [Co] follows
+};
+struct ActStackArgs {
+    const float* params;
+    const float* in;  int64_t in_stride;  int in_off;   // row r: macro at in + r*in_stride, micro image in_off after it
+    int macro_len;
+    float* F;         int64_t F_stride;                 // dense input [n][F_stride] = cat(flatten(conv NC), macro)
+    float* shares;                                      // [n][G][Co_last * Ho_last * Wo_last] split-K shares of conv NC
+    uint32_t* tickets;                                  // row group g's arrival counter at tickets[-g] (the MLP kernel's)
+    int n, R, NC, G;                                    // R rows per row group; conv NC-1's channels over G workgroups
+    int buf0, buf1, wred;                               // LDS floats (act_stack_plan): ping, pong, redundant convs' params
+    ActConvGeom L[DQNX_MAX_CONV];
+};
+size_t act_stack_plan(ActStackArgs& a);   // fills buf0 / buf1 / wred from NC, G, L; the launch's LDS bytes
+int launch_act_conv_stack(const ActStackArgs& a, hipStream_t s);
 int act_rows_per_block(int n, int ld);
 uint64_t act_scratch_bytes(int n, int h0, int ld, int L, int out1);
 int launch_act(const ActArgs& a, hipStream_t s);

@@ -95,7 +95,7 @@ EXPORTS = [
     "dqnx_params_modified", "dqnx_dp_bucket_count", "dqnx_dp_bucket_info", "dqnx_learn_step_bucket",
     "dqnx_apply_grads_bucket", "dqnx_ctrl_get_async", "dqnx_rng_sample_words", "dqnx_rng_advance",
     "dqnx_agent_stage_rng", "dqnx_agent_launch", "dqnx_agent_readback", "dqnx_act_host_scratch_bytes",
-    "dqnx_act_host", "dqnx_agent_learn_mt", "dqnx_agent_quiesce", "dqnx_agent_choose",
+    "dqnx_act_host", "dqnx_agent_learn_mt", "dqnx_agent_quiesce", "dqnx_agent_choose", "dqnx_act_kernel_count",
 ]
 
 GIL_HELD = ("dqnx_agent_learn_mt", "dqnx_agent_choose")   # entry points called with the GIL held (see lib())
@@ -165,6 +165,7 @@ def lib():
         "dqnx_set_agent_step": ([vp, I64, vp], ctypes.c_int),
         "dqnx_act": ([P(NetDesc), vp, vp, I32, vp, vp, vp, ctypes.c_uint64, vp], ctypes.c_int),
         "dqnx_act_scratch_bytes": ([P(NetDesc), I32], ctypes.c_uint64),
+        "dqnx_act_kernel_count": ([P(NetDesc), I32, P(I32)], ctypes.c_int),
         "dqnx_ctrl_get_async": ([vp, vp, vp], ctypes.c_int),
         "dqnx_rng_sample_words": ([vp, I64, I32, vp, P(I64)], ctypes.c_int),
         "dqnx_rng_advance": ([vp, I64, vp], ctypes.c_int),

@@ -285,7 +285,7 @@ class Agent:
         """choose_actions as ONE library call (dqnx_agent_choose): the acting kernel on the engine's online
         parameters, the epsilon-greedy draws of R:dqn/agent.py:95-97 on the live `random` generator in
         place (while the kernel runs), the wait (GIL released) and the last learn step's readback checks.
-        None when that path does not apply (the generator's layout unconfirmed, a non-MLP body, device
+        None when that path does not apply (the generator's layout unconfirmed, a body dqnx_act refuses, device
         observations, more than CHOOSE_MAX_ENVS rows): the method-by-method path runs instead."""
         if self._mt is None or isinstance(obses, T.Tensor):
             return None
@@ -321,7 +321,7 @@ class Agent:
         net = self.online_network
         na = net._native_act()
         spec = self.engine.spec
-        if na is None or spec.kind != C.DQNX_NET_MLP or na[1] is not self.engine.params:
+        if na is None or na[1] is not self.engine.params:   # (None: act_supported says no)
             return None
         L = C.lib()
         desc = spec.to_c()

@@ -41,7 +41,7 @@ def main():
 
 def measure(net):
     out = {}
-    for n in (1, 8, 64):
+    for n in (1, 2, 8, 64):
         x = np.random.default_rng(n).random((n, 284), dtype=np.float32)
         xt = torch.from_numpy(x).cuda()
 
