@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define DQNX_ABI_VERSION 3
+#define DQNX_ABI_VERSION 4
 
 /* ---- status codes ---------------------------------------------------------------- */
 #define DQNX_OK 0
@@ -412,6 +412,98 @@ int dqnx_agent_choose(dqnx_engine* e, const float* obs_host, int32_t n, double e
 uint64_t dqnx_act_host_scratch_bytes(const dqnx_net_desc* net, int32_t n);
 int dqnx_act_host(const dqnx_net_desc* net, const float* params, const float* obs_host, int32_t n,
                   int32_t* actions_host, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/* ---- training-state snapshot (ABI 4): stop a run and continue it bit for bit -----------------
+ * Everything a learn step, a push or a sample reads that an earlier one wrote, as ONE
+ * self-describing little-endian blob in host memory (the reference keeps only the online weights,
+ * R:dqn/agent.py:112-128; its replay deque, Adam state and target net do not survive a restart).
+ *
+ * Blob layout:
+ *   [0, sizeof(dqnx_state_info))  the header below, as it lies in memory: magic, format version,
+ *                                 the fingerprint and the section table
+ *   then the sections, each at its table entry's `offset` (from the start of the blob, a multiple of
+ *   DQNX_STATE_ALIGN, at or past header_bytes, in table order without overlap) with exactly `bytes`
+ *   bytes.  dqnx_state_save writes them back to back in the order listed below (every size is a
+ *   multiple of 4, and the fp64 SumTree, written right after the control block, lands on a multiple
+ *   of 8), so total_bytes = sizeof(dqnx_state_info) + the sum of the section sizes.
+ *
+ * Sections (P = n_params, n = ring_size, D = net.obs_dim, C = capacity), each present exactly once:
+ *   DQNX_SEC_PARAMS / TARGET_PARAMS / ADAM_M / ADAM_V   P fp32 each (dqnx_net_param_info order)
+ *   DQNX_SEC_CTRL            the whole dqnx_ctrl (both MT19937 streams, ring size / write slot, Adam
+ *                            step, agent_step, SumTree max / min indices, loss, PER beta)
+ *   DQNX_SEC_SUMTREE         [2C-1] fp64, DQNX_ALGO_PER_DOUBLE only (absent otherwise)
+ *   DQNX_SEC_RING_OBS / RING_NEXT_OBS   [n][D] fp32: ring slots 0 .. n-1 in PHYSICAL order (a ring that
+ *                            has not wrapped fills slots 0 .. n-1; a full one holds all C), rows of D
+ *                            floats whatever the engine's row stride
+ *   DQNX_SEC_RING_ACT [n] int32, DQNX_SEC_RING_REW [n] fp32, DQNX_SEC_RING_DONE [n] fp32 (0 / 1)
+ * Not state, never stored: the gradient, the minibatch indices, Q / TD buffers, IS weights and the
+ * workspace (derived weight layouts, RNG block caches, bf16 ring copies, the Adam bias table: the
+ * loading engine rebuilds or invalidates them).  The blob grows with the fill, not the capacity.
+ *
+ * A valid blob has: the magic and version below; header_bytes = sizeof(dqnx_state_info); total_bytes
+ * <= the bytes given; a network dqnx_net_param_count accepts, with n_params parameters; algo,
+ * compute_dtype in their enums; capacity >= 1; 0 <= ring_size <= capacity; 0 <= ring_wptr <
+ * capacity, and ring_wptr = ring_size while ring_size < capacity; the sections above with the sizes
+ * the fingerprint gives (computed without 64-bit overflow), inside total_bytes; and a control block
+ * whose ring_size / ring_wptr equal the fingerprint's, whose MT positions are <= 624, whose SumTree
+ * indices lie in [0, 2C-1), whose adam_step is >= 0 and whose sticky error is 0. */
+#define DQNX_STATE_MAGIC 0x54415453584e5144ull   /* "DQNXSTAT" read as a little-endian uint64 */
+#define DQNX_STATE_VERSION 1
+#define DQNX_STATE_ALIGN 4
+#define DQNX_STATE_MAX_SECTIONS 16
+enum dqnx_state_section_id {
+    DQNX_SEC_PARAMS = 1, DQNX_SEC_TARGET_PARAMS = 2, DQNX_SEC_ADAM_M = 3, DQNX_SEC_ADAM_V = 4, DQNX_SEC_CTRL = 5,
+    DQNX_SEC_RING_OBS = 6, DQNX_SEC_RING_NEXT_OBS = 7, DQNX_SEC_RING_ACT = 8, DQNX_SEC_RING_REW = 9,
+    DQNX_SEC_RING_DONE = 10, DQNX_SEC_SUMTREE = 11
+};
+typedef struct dqnx_state_section {
+    uint32_t id;               /* dqnx_state_section_id */
+    uint32_t reserved;         /* 0 */
+    uint64_t offset;           /* from the start of the blob */
+    uint64_t bytes;
+} dqnx_state_section;
+typedef struct dqnx_state_info {
+    uint64_t magic;            /* DQNX_STATE_MAGIC */
+    uint32_t version;          /* DQNX_STATE_VERSION */
+    uint32_t header_bytes;     /* sizeof(dqnx_state_info) */
+    uint64_t total_bytes;      /* of the whole blob */
+    /* fingerprint */
+    dqnx_net_desc net;
+    int32_t algo;              /* dqnx_algo */
+    int32_t compute_dtype;     /* dqnx_compute_dtype of the saving engine (informative: may differ at load) */
+    int32_t per_numpy121;      /* of the saving engine (informative) */
+    int32_t n_sections;
+    int32_t reserved0;         /* 0 */
+    int64_t capacity;
+    int64_t n_params;
+    int64_t ring_size;
+    int64_t ring_wptr;
+    dqnx_state_section sections[DQNX_STATE_MAX_SECTIONS];   /* [n_sections] used, the rest zero */
+} dqnx_state_info;
+
+/* Bytes dqnx_state_save would write now (host only: from the engine's mirror of the ring size). */
+int dqnx_state_bytes(dqnx_engine* e, uint64_t* bytes);
+/* Write the blob into dst_host (`bytes` >= dqnx_state_bytes; *written = its size).  Synchronises
+ * `stream`.  DQNX_ESTATE while a prefetched minibatch is pending (as dqnx_replay_push), while an agent
+ * launch's control-block readback is unread or a staged RNG state awaits its launch, or between the
+ * buckets of a bucketed step; DQNX_EDEVICE when dqnx_ctrl.error is set (a faulted run is not a
+ * checkpoint). */
+int dqnx_state_save(dqnx_engine* e, void* dst_host, uint64_t bytes, uint64_t* written, void* stream);
+/* Restore a blob.  The whole blob is validated (as dqnx_state_inspect does) and matched against the
+ * engine before the first device write: the network description, the capacity and prioritised-or-not
+ * must equal the engine's (uniform algorithms DQN / DOUBLE may load each other's blobs); batch, lr,
+ * gamma, tau, world / rank, compute_dtype and per_numpy121 may differ.  Any mismatch: DQNX_EINVAL with
+ * a message naming the field, the engine untouched.  DQNX_ESTATE under dqnx_state_save's pending
+ * conditions.  Afterwards the engine behaves as if it had reached that state by itself: its ring
+ * mirrors are set, the derived weight layouts are marked stale (as dqnx_params_modified), the RNG block
+ * caches are invalidated, a bf16 engine's bf16 ring rows are regenerated from the restored fp32 rows,
+ * the agent fast path's expectations are cleared; the Adam bias table stays the engine's own (it
+ * follows ITS lr).  Cached graphs stay valid (they read the state through the arena).  Synchronises
+ * `stream`; src_host is free on return. */
+int dqnx_state_load(dqnx_engine* e, const void* src_host, uint64_t bytes, void* stream);
+/* Validate a blob (all of the rules above) and copy its header out (host only: no engine, no GPU).
+ * DQNX_EINVAL with a message naming what is wrong. */
+int dqnx_state_inspect(const void* blob, uint64_t bytes, dqnx_state_info* out);
 
 /* ---- kernel-level timing (bench.py roofline) ---------------------------------------
  * A learn step is an ordered list of kernel launches (sample, linear_fwd_l1.., head_td_loss,

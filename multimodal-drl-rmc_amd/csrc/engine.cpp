@@ -4483,6 +4483,334 @@ int dqnx_agent_choose(dqnx_engine* e, const float* obs_host, int32_t n, double e
     return prev_rc;
 }
 
+// ---- training-state snapshot (dqnx.h: blob layout, what is state, the pending-state rules) ------
+struct StateSec {
+    uint32_t id;
+    int buf;            // the arena region it restores
+    const char* name;
+};
+static const StateSec kStateSecs[] = {
+    {DQNX_SEC_PARAMS, DQNX_BUF_PARAMS, "params"},
+    {DQNX_SEC_TARGET_PARAMS, DQNX_BUF_TARGET_PARAMS, "target_params"},
+    {DQNX_SEC_ADAM_M, DQNX_BUF_ADAM_M, "adam_m"},
+    {DQNX_SEC_ADAM_V, DQNX_BUF_ADAM_V, "adam_v"},
+    {DQNX_SEC_CTRL, DQNX_BUF_CTRL, "ctrl"},
+    {DQNX_SEC_SUMTREE, DQNX_BUF_SUMTREE, "sumtree"},   // (file order: 8-byte aligned here without padding)
+    {DQNX_SEC_RING_OBS, DQNX_BUF_RING_OBS, "ring_obs"},
+    {DQNX_SEC_RING_NEXT_OBS, DQNX_BUF_RING_NEXT_OBS, "ring_next_obs"},
+    {DQNX_SEC_RING_ACT, DQNX_BUF_RING_ACT, "ring_act"},
+    {DQNX_SEC_RING_REW, DQNX_BUF_RING_REW, "ring_rew"},
+    {DQNX_SEC_RING_DONE, DQNX_BUF_RING_DONE, "ring_done"},
+};
+constexpr int kStateSecCount = (int)(sizeof(kStateSecs) / sizeof(kStateSecs[0]));
+constexpr uint32_t kStateMaxId = DQNX_SEC_SUMTREE;
+static_assert(kStateSecCount <= DQNX_STATE_MAX_SECTIONS, "section table too small");
+static_assert(sizeof(dqnx_state_info) % 8 == 0 && sizeof(dqnx_state_section) == 24, "blob header layout");
+
+// Bytes of every section (indexed by id; 0 = absent) that a fingerprint implies, without 64-bit
+// overflow (false: a product overflowed -- nothing an engine could hold).
+static bool state_section_bytes(int64_t P, int64_t D, int64_t n, int64_t cap, bool per, uint64_t out[kStateMaxId + 1]) {
+    for (uint32_t i = 0; i <= kStateMaxId; i++) out[i] = 0;
+    uint64_t pb, row, rows, scal, tree;
+    if (P < 0 || D < 0 || n < 0 || cap < 1) return false;
+    if (__builtin_mul_overflow((uint64_t)P, (uint64_t)4, &pb)) return false;
+    if (__builtin_mul_overflow((uint64_t)D, (uint64_t)4, &row) || __builtin_mul_overflow((uint64_t)n, row, &rows)) return false;
+    if (__builtin_mul_overflow((uint64_t)n, (uint64_t)4, &scal)) return false;
+    if (__builtin_mul_overflow((uint64_t)cap, (uint64_t)2, &tree) || __builtin_mul_overflow(tree - 1, (uint64_t)8, &tree))
+        return false;
+    out[DQNX_SEC_PARAMS] = out[DQNX_SEC_TARGET_PARAMS] = out[DQNX_SEC_ADAM_M] = out[DQNX_SEC_ADAM_V] = pb;
+    out[DQNX_SEC_CTRL] = sizeof(dqnx_ctrl);
+    out[DQNX_SEC_RING_OBS] = out[DQNX_SEC_RING_NEXT_OBS] = rows;
+    out[DQNX_SEC_RING_ACT] = out[DQNX_SEC_RING_REW] = out[DQNX_SEC_RING_DONE] = scal;
+    out[DQNX_SEC_SUMTREE] = per ? tree : 0;
+    return true;
+}
+
+// The header of the blob an engine with `n` stored transitions writes; returns its total bytes.
+static uint64_t state_header(const dqnx_engine* e, int64_t n, int64_t wptr, dqnx_state_info* h) {
+    memset(h, 0, sizeof(*h));
+    const dqnx_config& c = e->cfg;
+    const bool per = c.algo == DQNX_ALGO_PER_DOUBLE;
+    h->magic = DQNX_STATE_MAGIC;
+    h->version = DQNX_STATE_VERSION;
+    h->header_bytes = (uint32_t)sizeof(dqnx_state_info);
+    h->net = c.net;
+    h->algo = c.algo;
+    h->compute_dtype = c.compute_dtype;
+    h->per_numpy121 = c.per_numpy121;
+    h->capacity = c.capacity;
+    h->n_params = e->np.P;
+    h->ring_size = n;
+    h->ring_wptr = wptr;
+    uint64_t sz[kStateMaxId + 1];
+    (void)state_section_bytes(e->np.P, c.net.obs_dim, n, c.capacity, per, sz);   // (an engine's own sizes fit)
+    uint64_t cur = align_up(sizeof(dqnx_state_info), DQNX_STATE_ALIGN);
+    int k = 0;
+    for (int i = 0; i < kStateSecCount; i++) {
+        const uint32_t id = kStateSecs[i].id;
+        if (id == DQNX_SEC_SUMTREE && !per) continue;
+        h->sections[k].id = id;
+        h->sections[k].offset = cur;
+        h->sections[k].bytes = sz[id];
+        cur = align_up(cur + sz[id], DQNX_STATE_ALIGN);
+        k++;
+    }
+    h->n_sections = k;
+    h->total_bytes = cur;
+    return cur;
+}
+
+// Every rule of dqnx.h's "A valid blob has"; *h = the header; sec[id] = its table entry (or null).
+static int state_validate(const void* blob, uint64_t bytes, dqnx_state_info* h, const dqnx_state_section* sec[kStateMaxId + 1]) {
+    if (!blob || !h) return set_error(DQNX_EINVAL, "null argument");
+    if (bytes < sizeof(dqnx_state_info))
+        return set_error(DQNX_EINVAL, "state blob truncated: %llu bytes, the header alone is %zu", (unsigned long long)bytes,
+                         sizeof(dqnx_state_info));
+    memcpy(h, blob, sizeof(*h));   // (the caller's pointer may be unaligned)
+    if (h->magic != DQNX_STATE_MAGIC) return set_error(DQNX_EINVAL, "not a dqnx state blob (bad magic)");
+    if (h->version < 1 || h->version > DQNX_STATE_VERSION)
+        return set_error(DQNX_EINVAL, "state blob format version %u, this library reads up to %d", h->version, DQNX_STATE_VERSION);
+    if (h->header_bytes != sizeof(dqnx_state_info))
+        return set_error(DQNX_EINVAL, "state blob header_bytes %u, expected %zu", h->header_bytes, sizeof(dqnx_state_info));
+    if (h->total_bytes < h->header_bytes || h->total_bytes % DQNX_STATE_ALIGN)
+        return set_error(DQNX_EINVAL, "state blob total_bytes %llu is malformed", (unsigned long long)h->total_bytes);
+    if (h->total_bytes > bytes)
+        return set_error(DQNX_EINVAL, "state blob truncated: %llu bytes of %llu", (unsigned long long)bytes,
+                         (unsigned long long)h->total_bytes);
+    if (h->algo < DQNX_ALGO_DQN || h->algo > DQNX_ALGO_PER_DOUBLE) return set_error(DQNX_EINVAL, "state blob: bad algo %d", h->algo);
+    if (h->compute_dtype != DQNX_COMPUTE_FP32 && h->compute_dtype != DQNX_COMPUTE_BF16)
+        return set_error(DQNX_EINVAL, "state blob: bad compute_dtype %d", h->compute_dtype);
+    if (h->reserved0) return set_error(DQNX_EINVAL, "state blob: reserved header word set");
+    if (h->capacity < 1) return set_error(DQNX_EINVAL, "state blob: capacity %lld out of range", (long long)h->capacity);
+    if (h->ring_size < 0 || h->ring_size > h->capacity)
+        return set_error(DQNX_EINVAL, "state blob: ring_size %lld not in [0, capacity %lld]", (long long)h->ring_size,
+                         (long long)h->capacity);
+    if (h->ring_wptr < 0 || h->ring_wptr >= h->capacity)
+        return set_error(DQNX_EINVAL, "state blob: ring_wptr %lld not in [0, capacity %lld)", (long long)h->ring_wptr,
+                         (long long)h->capacity);
+    if (h->ring_size < h->capacity && h->ring_wptr != h->ring_size)
+        return set_error(DQNX_EINVAL, "state blob: ring_wptr %lld of a ring that has not wrapped (ring_size %lld)",
+                         (long long)h->ring_wptr, (long long)h->ring_size);
+    NetPlan np;
+    int rc = plan_net(&h->net, np);
+    if (rc) return rc;
+    if (h->n_params != np.P)
+        return set_error(DQNX_EINVAL, "state blob: n_params %lld, its network has %lld", (long long)h->n_params, (long long)np.P);
+    const bool per = h->algo == DQNX_ALGO_PER_DOUBLE;
+    uint64_t want[kStateMaxId + 1];
+    if (!state_section_bytes(np.P, h->net.obs_dim, h->ring_size, h->capacity, per, want))
+        return set_error(DQNX_EINVAL, "state blob: section sizes of ring_size %lld x obs_dim %d, capacity %lld overflow 64 bits",
+                         (long long)h->ring_size, h->net.obs_dim, (long long)h->capacity);
+    if (h->n_sections < 0 || h->n_sections > DQNX_STATE_MAX_SECTIONS)
+        return set_error(DQNX_EINVAL, "state blob: n_sections %d", h->n_sections);
+    for (uint32_t i = 0; i <= kStateMaxId; i++) sec[i] = nullptr;
+    uint64_t prev_end = h->header_bytes;
+    for (int i = 0; i < DQNX_STATE_MAX_SECTIONS; i++) {
+        const dqnx_state_section& s = h->sections[i];
+        if (i >= h->n_sections) {
+            if (s.id || s.reserved || s.offset || s.bytes) return set_error(DQNX_EINVAL, "state blob: unused section entry %d not zero", i);
+            continue;
+        }
+        if (s.id < 1 || s.id > kStateMaxId || s.reserved) return set_error(DQNX_EINVAL, "state blob: section entry %d has unknown id %u", i, s.id);
+        if (sec[s.id]) return set_error(DQNX_EINVAL, "state blob: section %u appears twice", s.id);
+        if (s.id == DQNX_SEC_SUMTREE && !per) return set_error(DQNX_EINVAL, "state blob: a SumTree section without prioritised replay");
+        uint64_t end;
+        if (s.offset % DQNX_STATE_ALIGN || s.offset < prev_end || __builtin_add_overflow(s.offset, s.bytes, &end) ||
+            end > h->total_bytes)
+            return set_error(DQNX_EINVAL, "state blob: section %u [offset %llu, %llu bytes) outside the blob's %llu bytes or out of order",
+                             s.id, (unsigned long long)s.offset, (unsigned long long)s.bytes, (unsigned long long)h->total_bytes);
+        if (s.bytes != want[s.id])
+            return set_error(DQNX_EINVAL, "state blob: section %u holds %llu bytes, the fingerprint implies %llu", s.id,
+                             (unsigned long long)s.bytes, (unsigned long long)want[s.id]);
+        prev_end = end;
+        sec[s.id] = &s;
+    }
+    for (int i = 0; i < kStateSecCount; i++) {
+        const uint32_t id = kStateSecs[i].id;
+        if (!sec[id] && (id != DQNX_SEC_SUMTREE || per)) return set_error(DQNX_EINVAL, "state blob: section %s missing", kStateSecs[i].name);
+    }
+    dqnx_ctrl ct;
+    memcpy(&ct, (const char*)blob + sec[DQNX_SEC_CTRL]->offset, sizeof(ct));
+    if (ct.ring_size != h->ring_size || ct.ring_wptr != h->ring_wptr)
+        return set_error(DQNX_EINVAL, "state blob: control block ring_size / ring_wptr differ from the fingerprint");
+    if (ct.py_mt[624] > 624 || ct.np_mt[624] > 624) return set_error(DQNX_EINVAL, "state blob: MT position > 624");
+    uint64_t nodes = 0;   // 2 * capacity - 1 (did not overflow above)
+    (void)__builtin_mul_overflow((uint64_t)h->capacity, (uint64_t)2, &nodes);
+    nodes -= 1;
+    if (ct.per_max_idx < 0 || (uint64_t)ct.per_max_idx >= nodes || ct.per_min_idx < 0 || (uint64_t)ct.per_min_idx >= nodes)
+        return set_error(DQNX_EINVAL, "state blob: SumTree max / min index outside the tree");
+    if (ct.adam_step < 0) return set_error(DQNX_EINVAL, "state blob: negative adam_step");
+    if (ct.error) return set_error(DQNX_EINVAL, "state blob: saved with device error %d set", ct.error);
+    return DQNX_OK;
+}
+
+// the calls a snapshot may not fall between
+static int state_pending(const dqnx_engine* e, const char* what) {
+    if (e->pf_valid) return set_error(DQNX_ESTATE, "%s while a prefetched minibatch is pending", what);
+    if (e->ag_ctrl_live) return set_error(DQNX_ESTATE, "%s while an agent launch's control-block readback is unread", what);
+    if (e->ag_which >= 0) return set_error(DQNX_ESTATE, "%s while a staged RNG state awaits its agent launch", what);
+    if (e->bucket_key >= 0) return set_error(DQNX_ESTATE, "%s between the buckets of a bucketed step", what);
+    return DQNX_OK;
+}
+
+int dqnx_state_inspect(const void* blob, uint64_t bytes, dqnx_state_info* out) {
+    dqnx_state_info h;
+    const dqnx_state_section* sec[kStateMaxId + 1];
+    if (!out) return set_error(DQNX_EINVAL, "null argument");
+    int rc = state_validate(blob, bytes, &h, sec);
+    if (rc) return rc;
+    *out = h;
+    return DQNX_OK;
+}
+
+int dqnx_state_bytes(dqnx_engine* e, uint64_t* bytes) {
+    if (!e || !bytes) return set_error(DQNX_EINVAL, "null argument");
+    dqnx_state_info h;
+    *bytes = state_header(e, e->ring_size, e->ring_wptr, &h);
+    return DQNX_OK;
+}
+
+int dqnx_state_save(dqnx_engine* e, void* dst_host, uint64_t bytes, uint64_t* written, void* stream) {
+    int rc = check_bound(e);
+    if (rc) return rc;
+    if (!dst_host || !written) return set_error(DQNX_EINVAL, "null argument");
+    *written = 0;
+    rc = state_pending(e, "state save");
+    if (rc) return rc;
+    dqnx_state_info h;
+    const uint64_t total = state_header(e, e->ring_size, e->ring_wptr, &h);
+    if (bytes < total)
+        return set_error(DQNX_EINVAL, "state save: %llu bytes given, the blob takes %llu", (unsigned long long)bytes,
+                         (unsigned long long)total);
+    hipStream_t s = (hipStream_t)stream;
+    DQNX_HIP_CHECK(hipStreamSynchronize(s));
+    char* dst = (char*)dst_host;
+    memcpy(dst, &h, sizeof(h));
+    uint64_t prev_end = sizeof(h);
+    const int D = e->cfg.net.obs_dim;
+    const int64_t n = e->ring_size;
+    for (int i = 0; i < h.n_sections; i++) {
+        const dqnx_state_section& sc = h.sections[i];
+        memset(dst + prev_end, 0, sc.offset - prev_end);   // the gaps are zero
+        prev_end = sc.offset + sc.bytes;
+        if (!sc.bytes) continue;
+        int buf = -1;
+        for (int j = 0; j < kStateSecCount; j++)
+            if (kStateSecs[j].id == sc.id) buf = kStateSecs[j].buf;
+        const char* src = e->arena + e->off[buf];
+        if ((sc.id == DQNX_SEC_RING_OBS || sc.id == DQNX_SEC_RING_NEXT_OBS) && e->stride != D) {
+            DQNX_HIP_CHECK(hipMemcpy2DAsync(dst + sc.offset, (size_t)D * 4, src, (size_t)e->stride * 4, (size_t)D * 4, (size_t)n,
+                                            hipMemcpyDeviceToHost, s));
+        } else {
+            DQNX_HIP_CHECK(hipMemcpyAsync(dst + sc.offset, src, sc.bytes, hipMemcpyDeviceToHost, s));
+        }
+    }
+    memset(dst + prev_end, 0, total - prev_end);
+    DQNX_HIP_CHECK(hipStreamSynchronize(s));
+    dqnx_ctrl ct;
+    for (int i = 0; i < h.n_sections; i++)
+        if (h.sections[i].id == DQNX_SEC_CTRL) memcpy(&ct, dst + h.sections[i].offset, sizeof(ct));
+    if (ct.error) return set_error(DQNX_EDEVICE, "state save: device error %d is set (a faulted run is not a checkpoint)", ct.error);
+    if (ct.ring_size != e->ring_size || ct.ring_wptr != e->ring_wptr)
+        return set_error(DQNX_ESTATE, "state save: the control block's ring state (%lld, %lld) differs from the host mirror (%lld, %lld)",
+                         (long long)ct.ring_size, (long long)ct.ring_wptr, (long long)e->ring_size, (long long)e->ring_wptr);
+    *written = total;
+    return DQNX_OK;
+}
+
+#define DQNX_STATE_MATCH(field)                                                                                  \
+    if (h.net.field != c.net.field)                                                                              \
+        return set_error(DQNX_EINVAL, "state load: the blob's net." #field " is %d, the engine's %d", (int)h.net.field, \
+                         (int)c.net.field)
+
+int dqnx_state_load(dqnx_engine* e, const void* src_host, uint64_t bytes, void* stream) {
+    int rc = check_bound(e);
+    if (rc) return rc;
+    rc = state_pending(e, "state load");
+    if (rc) return rc;
+    dqnx_state_info h;
+    const dqnx_state_section* sec[kStateMaxId + 1];
+    rc = state_validate(src_host, bytes, &h, sec);
+    if (rc) return rc;
+    const dqnx_config& c = e->cfg;
+    DQNX_STATE_MATCH(kind);
+    DQNX_STATE_MATCH(head);
+    DQNX_STATE_MATCH(activation);
+    DQNX_STATE_MATCH(obs_dim);
+    DQNX_STATE_MATCH(n_actions);
+    DQNX_STATE_MATCH(n_dense);
+    for (int i = 0; i < c.net.n_dense; i++) DQNX_STATE_MATCH(dense[i]);
+    DQNX_STATE_MATCH(macro_len);
+    DQNX_STATE_MATCH(micro_c);
+    DQNX_STATE_MATCH(micro_h);
+    DQNX_STATE_MATCH(micro_w);
+    DQNX_STATE_MATCH(n_conv);
+    for (int i = 0; i < c.net.n_conv; i++) {
+        DQNX_STATE_MATCH(conv_out[i]);
+        DQNX_STATE_MATCH(conv_kh[i]);
+        DQNX_STATE_MATCH(conv_kw[i]);
+        DQNX_STATE_MATCH(conv_sh[i]);
+        DQNX_STATE_MATCH(conv_sw[i]);
+    }
+    if (h.n_params != e->np.P)
+        return set_error(DQNX_EINVAL, "state load: the blob's n_params is %lld, the engine's %lld", (long long)h.n_params,
+                         (long long)e->np.P);
+    if (h.capacity != c.capacity)
+        return set_error(DQNX_EINVAL, "state load: the blob's capacity is %lld, the engine's %lld", (long long)h.capacity,
+                         (long long)c.capacity);
+    const bool per = c.algo == DQNX_ALGO_PER_DOUBLE;
+    if ((h.algo == DQNX_ALGO_PER_DOUBLE) != per)
+        return set_error(DQNX_EINVAL, "state load: the blob's algo is %d, the engine's %d (prioritised and uniform replay do not mix)",
+                         h.algo, c.algo);
+    // ---- valid and matching: the device writes, stream-ordered after everything enqueued on s ----
+    hipStream_t s = (hipStream_t)stream;
+    const char* src = (const char*)src_host;
+    const int D = c.net.obs_dim;
+    const int64_t n = h.ring_size;
+    for (int j = 0; j < kStateSecCount; j++) {
+        const dqnx_state_section* sc = sec[kStateSecs[j].id];
+        if (!sc || !sc->bytes) continue;
+        char* dst = e->arena + e->off[kStateSecs[j].buf];
+        if ((sc->id == DQNX_SEC_RING_OBS || sc->id == DQNX_SEC_RING_NEXT_OBS) && e->stride != D) {
+            DQNX_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)e->stride * 4, src + sc->offset, (size_t)D * 4, (size_t)D * 4, (size_t)n,
+                                            hipMemcpyHostToDevice, s));
+        } else {
+            DQNX_HIP_CHECK(hipMemcpyAsync(dst, src + sc->offset, sc->bytes, hipMemcpyHostToDevice, s));
+        }
+    }
+    // derived data: the RNG block caches hold successors of the old streams (header word 0 = blocks held)
+    DQNX_HIP_CHECK(hipMemsetAsync(e->arena + e->ws_mtc, 0, 256, s));
+    if (e->ws_npc) DQNX_HIP_CHECK(hipMemsetAsync(e->arena + e->ws_npc, 0, 256, s));
+    if (e->stride16 && n > 0) {   // a bf16 engine gathers the bf16 copies of the rows
+        Ring16Args ra;
+        memset(&ra, 0, sizeof(ra));
+        ra.ring_obs = at<float>(e, e->off[DQNX_BUF_RING_OBS]);
+        ra.ring_next = at<float>(e, e->off[DQNX_BUF_RING_NEXT_OBS]);
+        ra.ring16_obs = at<uint16_t>(e, e->ws_ring16[0]);
+        ra.ring16_next = at<uint16_t>(e, e->ws_ring16[1]);
+        ra.rows = n;
+        ra.capacity = c.capacity;
+        ra.obs_dim = D;
+        ra.stride = e->stride;
+        ra.stride16 = e->stride16;
+        rc = launch_ring16_rebuild(ra, s);
+        if (rc) return rc;
+    }
+    DQNX_HIP_CHECK(hipStreamSynchronize(s));   // src_host is the caller's again
+    e->ring_size = h.ring_size;
+    e->ring_wptr = h.ring_wptr;
+    e->wblk_dirty = true;    // as dqnx_params_modified: the next step rebuilds the blocked / permuted copies
+    e->perm_dirty = true;
+    e->pf_valid = false;
+    e->pf_inlaunch = false;
+    e->pf_computed_valid[0] = e->pf_computed_valid[1] = false;
+    e->ag_expect_live = false;
+    e->ag_check_live = false;
+    e->ag_which = -1;
+    return DQNX_OK;
+}
+#undef DQNX_STATE_MATCH
+
 int dqnx_debug_stamps(dqnx_engine* e, int64_t* out64, void* stream) {
 #ifdef DQNX_STAMPS
     int rc = check_bound(e);

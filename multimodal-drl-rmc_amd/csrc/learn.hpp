@@ -835,6 +835,16 @@ int launch_act(const ActArgs& a, hipStream_t s);
 int launch_soft_update(float* target, const float* p, int64_t n, float tau, float omt, hipStream_t s);
 int launch_copy_i32x2(int32_t* d0, const int32_t* s0, int n0, int32_t* d1, const int32_t* s1, int n1, hipStream_t s);
 int launch_replay_push(const PushArgs& a, hipStream_t s);
+// dqnx_state_load on a bf16 engine (state.hip): ring16 rows [0, rows) from the fp32 ring rows
+struct Ring16Args {
+    const float* ring_obs;
+    const float* ring_next;
+    uint16_t* ring16_obs;
+    uint16_t* ring16_next;
+    int64_t rows, capacity;      // rows <= capacity
+    int obs_dim, stride, stride16;
+};
+int launch_ring16_rebuild(const Ring16Args& a, hipStream_t s);
 
 int launch_sample_uniform(const SampleArgs& a, hipStream_t s);
 int launch_idx_to_phys(const int32_t* idx, int32_t* phys, int shard_begin, int n, dqnx_ctrl* ctrl, int64_t capacity,

@@ -82,6 +82,32 @@ class Ctrl(ctypes.Structure):
     ]
 
 
+# training-state snapshot (dqnx.h "training-state snapshot")
+STATE_MAGIC = 0x54415453584E5144   # b"DQNXSTAT" little-endian
+STATE_VERSION = 1
+STATE_ALIGN = 4
+STATE_MAX_SECTIONS = 16
+(SEC_PARAMS, SEC_TARGET_PARAMS, SEC_ADAM_M, SEC_ADAM_V, SEC_CTRL, SEC_RING_OBS, SEC_RING_NEXT_OBS, SEC_RING_ACT,
+ SEC_RING_REW, SEC_RING_DONE, SEC_SUMTREE) = range(1, 12)
+SEC_NAMES = {SEC_PARAMS: "params", SEC_TARGET_PARAMS: "target_params", SEC_ADAM_M: "adam_m", SEC_ADAM_V: "adam_v",
+             SEC_CTRL: "ctrl", SEC_RING_OBS: "ring_obs", SEC_RING_NEXT_OBS: "ring_next_obs", SEC_RING_ACT: "ring_act",
+             SEC_RING_REW: "ring_rew", SEC_RING_DONE: "ring_done", SEC_SUMTREE: "sumtree"}
+
+
+class StateSection(ctypes.Structure):
+    _fields_ = [("id", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("offset", ctypes.c_uint64),
+                ("bytes", ctypes.c_uint64)]
+
+
+class StateInfo(ctypes.Structure):
+    _fields_ = [
+        ("magic", ctypes.c_uint64), ("version", ctypes.c_uint32), ("header_bytes", ctypes.c_uint32),
+        ("total_bytes", ctypes.c_uint64), ("net", NetDesc), ("algo", I32), ("compute_dtype", I32),
+        ("per_numpy121", I32), ("n_sections", I32), ("reserved0", I32), ("capacity", I64), ("n_params", I64),
+        ("ring_size", I64), ("ring_wptr", I64), ("sections", StateSection * STATE_MAX_SECTIONS),
+    ]
+
+
 # every symbol the header declares (checked by tests/test_capi.py)
 EXPORTS = [
     "dqnx_net_param_count", "dqnx_net_param_info", "dqnx_config_defaults", "dqnx_engine_create",
@@ -96,6 +122,7 @@ EXPORTS = [
     "dqnx_apply_grads_bucket", "dqnx_ctrl_get_async", "dqnx_rng_sample_words", "dqnx_rng_advance",
     "dqnx_agent_stage_rng", "dqnx_agent_launch", "dqnx_agent_readback", "dqnx_act_host_scratch_bytes",
     "dqnx_act_host", "dqnx_agent_learn_mt", "dqnx_agent_quiesce", "dqnx_agent_choose", "dqnx_act_kernel_count",
+    "dqnx_state_bytes", "dqnx_state_save", "dqnx_state_load", "dqnx_state_inspect",
 ]
 
 GIL_HELD = ("dqnx_agent_learn_mt", "dqnx_agent_choose")   # entry points called with the GIL held (see lib())
@@ -177,6 +204,10 @@ def lib():
         "dqnx_agent_choose": ([vp, vp, I32, ctypes.c_double, vp, vp, vp, vp, ctypes.c_uint64, I32, vp], ctypes.c_int),
         "dqnx_act_host_scratch_bytes": ([P(NetDesc), I32], ctypes.c_uint64),
         "dqnx_act_host": ([P(NetDesc), vp, vp, I32, vp, vp, ctypes.c_uint64, vp], ctypes.c_int),
+        "dqnx_state_bytes": ([vp, P(ctypes.c_uint64)], ctypes.c_int),
+        "dqnx_state_save": ([vp, vp, ctypes.c_uint64, P(ctypes.c_uint64), vp], ctypes.c_int),
+        "dqnx_state_load": ([vp, vp, ctypes.c_uint64, vp], ctypes.c_int),
+        "dqnx_state_inspect": ([vp, ctypes.c_uint64, P(StateInfo)], ctypes.c_int),
     }
     # dqnx_agent_learn_mt reads and writes random._inst's MT words in place: call it through a PyDLL
     # handle, which keeps the GIL for the call (a CDLL call releases it, and another thread's `random`
@@ -195,5 +226,7 @@ def lib():
 def check(rc: int, what: str = ""):
     if rc != DQNX_OK:
         msg = lib().dqnx_last_error().decode(errors="replace")
-        raise DqnxError(f"{what}: dqnx error {rc}: {msg}")
+        err = DqnxError(f"{what}: dqnx error {rc}: {msg}")
+        err.code = rc   # the DQNX_E* status, for callers that tell refusals apart
+        raise err
     return rc

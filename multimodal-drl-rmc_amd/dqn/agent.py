@@ -46,6 +46,7 @@ import array
 import ctypes
 import os
 import random
+import struct
 import time
 from collections import deque
 from datetime import timedelta
@@ -57,6 +58,16 @@ from . import _capi as C
 from .engine import LearnEngine, raise_device_error, spec_from_body
 from .network import DeepQNetwork, DuelingDeepQNetwork
 from .replay_memory import ReplayMemoryNaive, ReplayMemoryPrioritized
+from .utils import pack
+
+_STATE_MAGIC = b"DQNXAGNT"   # save_training_state files (the engine blob inside has its own magic)
+_STATE_VERSION = 1
+
+
+def _train_state_on() -> bool:
+    """DQNX_TRAIN_STATE=1: save_model() / load_model() also write / restore the whole training state
+    (save_path + '.state'), for an unmodified train.py.  Unset (default): the reference's behaviour."""
+    return os.environ.get("DQNX_TRAIN_STATE", "0") not in ("", "0")
 
 
 def _summary_writer(log_dir):
@@ -420,6 +431,81 @@ class Agent:
         elif self.target_soft_update:
             self.engine.soft_update()
 
+    # -- whole training state (no reference counterpart: R:dqn/agent.py:112-128 keeps the online weights
+    #    only, so a restarted run refills its replay memory and starts Adam, the target net and the PER
+    #    tree over) ------------------------------------------------------------------------------------
+    def _agent_state(self):
+        """The agent's own state beside the engine blob, as plain values for dqn/utils/pack.py's codec."""
+        pv, pmt, pg = random.getstate()
+        nk, nmt, npos, nhas, ncached = np.random.get_state()
+        return {"step": int(self.step), "resume_step": int(self.resume_step), "episode_count": int(self.episode_count),
+                "ep_info": [[float(e['r']), float(e['l'])] for e in self.ep_info_buffer],
+                "py_rng": {"version": int(pv), "mt": np.asarray(pmt, dtype=np.uint32), "gauss": pg},
+                "np_rng": {"kind": str(nk), "mt": np.asarray(nmt, dtype=np.uint32), "pos": int(npos),
+                           "has_gauss": int(nhas), "cached": float(ncached)},
+                "learn_step_at": getattr(self, "_learn_step_at", None)}
+
+    def save_training_state(self, path):
+        """Everything a resumed run needs to continue bit for bit: the engine's state blob (both nets, Adam
+        moments and step, replay ring, SumTree, both device RNG streams, PER beta step;
+        LearnEngine.save_state) and the agent's own (`step`, `resume_step`, `episode_count`,
+        `ep_info_buffer`, the `random` and `np.random` generators, the PER agent's learn step).
+        File: _STATE_MAGIC, u32 version, u64 length of the packed agent dict, the dict, zero padding to
+        64 bytes, the engine blob.  Written to a temporary name and moved into place."""
+        self.flush()
+        meta = pack.dumps(self._agent_state())
+        head = _STATE_MAGIC + struct.pack("<IQ", _STATE_VERSION, len(meta)) + meta
+        head += b"\0" * (-len(head) % 64)
+        d = os.path.dirname(path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        tmp = path + ".tmp"
+        with open(tmp, "wb") as f:
+            f.write(head)
+            self.engine.save_state(f)
+        os.replace(tmp, path)
+
+    @staticmethod
+    def _read_training_state(path, meta_only=False):
+        """-> (agent dict, engine blob as a uint8 array; None with meta_only) of a save_training_state file."""
+        fixed = len(_STATE_MAGIC) + 12
+        with open(path, "rb") as f:
+            head = f.read(fixed)
+            if len(head) < fixed or head[:len(_STATE_MAGIC)] != _STATE_MAGIC:
+                raise ValueError(f"{path}: not a training-state file")
+            version, n = struct.unpack_from("<IQ", head, len(_STATE_MAGIC))
+            if version != _STATE_VERSION:
+                raise ValueError(f"{path}: training-state file version {version}, this code reads {_STATE_VERSION}")
+            packed = f.read(n)
+            if len(packed) < n:
+                raise ValueError(f"{path}: training-state file truncated")
+            meta = pack.loads(packed)
+            if meta_only:
+                return meta, None
+            f.read(-(fixed + n) % 64)
+            return meta, np.frombuffer(f.read(), dtype=np.uint8)
+
+    def load_training_state(self, path, restore_rng=True):
+        """Continue the run save_training_state wrote: the engine blob is validated and matched against
+        this agent's engine first (a blob that does not fit raises and changes nothing), then the agent's
+        own state follows.  restore_rng=False leaves `random` / `np.random` as they are."""
+        self.flush()
+        meta, blob = self._read_training_state(path)
+        self.engine.load_state_blob(blob)
+        self.step = int(meta["step"])
+        self.resume_step = int(meta["resume_step"])
+        self.episode_count = int(meta["episode_count"])
+        self.ep_info_buffer.clear()
+        self.ep_info_buffer.extend({'r': r, 'l': l} for r, l in meta["ep_info"])
+        if meta.get("learn_step_at") is not None:
+            self._learn_step_at = int(meta["learn_step_at"])
+        if restore_rng:
+            p, q = meta["py_rng"], meta["np_rng"]
+            random.setstate((int(p["version"]), tuple(int(x) for x in p["mt"]), p["gauss"]))
+            np.random.set_state((q["kind"], np.asarray(q["mt"], dtype=np.uint32), int(q["pos"]), int(q["has_gauss"]),
+                                 float(q["cached"])))
+        self._learn_pending = False
+
     # -- checkpoints / logging (R:dqn/agent.py:112-147) ---------------------------------
     def load_model(self):
         import os
@@ -432,6 +518,14 @@ class Agent:
              for _ in range(np.min([self.episode_count, self.ep_info_buffer.maxlen]))]
             print("Step: ", self.resume_step * self.n_env, ", Episodes: ", self.episode_count, ", Avg Rew: ",
                   rew_mean, ", Avg Ep Len: ", len_mean)
+            state = self.save_path + '.state'
+            if _train_state_on() and os.path.exists(state) and \
+                    int(self._read_training_state(state, meta_only=True)[0]["step"]) == int(self.resume_step):
+                # the whole run continues: target net, Adam, replay and RNG as saved, no hard update
+                self.load_training_state(state)
+                self.resume_step = self.step
+                print("Training state restored from " + state)
+                return
             self.update_target_network(force=True)
             self.step = self.resume_step
 
@@ -443,6 +537,8 @@ class Agent:
             T.cuda.synchronize(self.device)
             self.online_network.save(self.save_path, self.step, self.episode_count, self.info_mean('r'),
                                      self.info_mean('l'))
+            if _train_state_on():   # DQNX_TRAIN_STATE=1: the whole training state beside the .pack
+                self.save_training_state(self.save_path + '.state')
             print("OK!")
 
     def log(self):

@@ -572,6 +572,58 @@ class LearnEngine:
         C.check(self.L.dqnx_set_agent_step(self.h, int(step_times_n_env), self.stream()), "set_agent_step")
         self.agent_step = int(step_times_n_env)
 
+    # ---- training-state snapshot (dqnx_state_*: include/dqnx.h "training-state snapshot") ----------
+    def state_bytes(self) -> int:
+        """Bytes save_state would write now (grows with the ring's fill, not its capacity)."""
+        n = ctypes.c_uint64()
+        C.check(self.L.dqnx_state_bytes(self.h, ctypes.byref(n)), "state_bytes")
+        return int(n.value)
+
+    def state_blob(self) -> np.ndarray:
+        """The whole training state as one uint8 array (dqnx_state_save; synchronises the stream):
+        both parameter sets, the Adam moments, the control block (both RNG streams, Adam step, agent
+        step, PER beta), the filled ring rows and, for PER, the SumTree."""
+        self.launch_recorded()
+        buf = np.empty(self.state_bytes(), dtype=np.uint8)
+        w = ctypes.c_uint64()
+        C.check(self.L.dqnx_state_save(self.h, ctypes.c_void_p(buf.ctypes.data), buf.nbytes, ctypes.byref(w),
+                                       self.stream()), "state_save")
+        return buf[:int(w.value)]
+
+    def save_state(self, path_or_fileobj) -> int:
+        """Write the training state to a path or a binary file object; returns the bytes written."""
+        blob = self.state_blob()
+        if hasattr(path_or_fileobj, "write"):
+            path_or_fileobj.write(memoryview(blob))
+        else:
+            with open(path_or_fileobj, "wb") as f:
+                f.write(memoryview(blob))
+        return int(blob.nbytes)
+
+    def load_state_blob(self, blob) -> None:
+        """Restore a blob (bytes-like or uint8 array) written by an engine of the same network, capacity
+        and prioritised-or-not (dqnx_state_load); batch, lr, gamma, tau and compute_dtype may differ.  A
+        blob that does not fit raises DqnxError (code DQNX_EINVAL) naming the field and leaves the
+        engine as it was.  Refreshes the ring / agent-step mirrors this class keeps."""
+        self.launch_recorded()
+        a = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob).view(np.uint8)
+        C.check(self.L.dqnx_state_load(self.h, ctypes.c_void_p(a.ctypes.data), a.nbytes, self.stream()), "state_load")
+        info = inspect_state_blob(a)
+        self.ring_size = info["ring_size"]
+        self.ring_wptr = info["ring_wptr"]
+        off, n = info["sections"]["ctrl"]
+        self.agent_step = int(C.Ctrl.from_buffer_copy(a[off:off + n].tobytes()).agent_step)
+        self._ag_unread = False
+
+    def load_state(self, path_or_fileobj) -> None:
+        """load_state_blob from a path or a binary file object (read to its end)."""
+        if hasattr(path_or_fileobj, "read"):
+            data = path_or_fileobj.read()
+        else:
+            with open(path_or_fileobj, "rb") as f:
+                data = f.read()
+        self.load_state_blob(data)
+
     def ctrl(self) -> C.Ctrl:
         """Snapshot of the device control block (synchronises)."""
         self.launch_recorded()
@@ -583,6 +635,35 @@ class LearnEngine:
 
     def check_device_error(self):
         raise_device_error(self.ctrl().error)
+
+
+def inspect_state_blob(blob) -> dict:
+    """The fingerprint and section table of a training-state blob (dqnx_state_inspect: host only, no
+    engine, no GPU).  A blob that is not valid raises DqnxError (code DQNX_EINVAL) saying why."""
+    a = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob).view(np.uint8)
+    info = C.StateInfo()
+    C.check(C.lib().dqnx_state_inspect(ctypes.c_void_p(a.ctypes.data if a.size else None), a.nbytes,
+                                       ctypes.byref(info)), "state_inspect")
+    net = info.net
+    out = {
+        "version": int(info.version), "total_bytes": int(info.total_bytes),
+        "net": {"kind": net.kind, "head": net.head, "activation": net.activation, "obs_dim": net.obs_dim,
+                "n_actions": net.n_actions, "dense": tuple(net.dense[:net.n_dense]), "macro_len": net.macro_len,
+                "micro_chw": (net.micro_c, net.micro_h, net.micro_w),
+                "conv": tuple((net.conv_out[i], (net.conv_kh[i], net.conv_kw[i]), (net.conv_sh[i], net.conv_sw[i]))
+                              for i in range(net.n_conv))},
+        "algo": int(info.algo), "capacity": int(info.capacity), "compute_dtype": int(info.compute_dtype),
+        "per_numpy121": int(info.per_numpy121), "n_params": int(info.n_params), "ring_size": int(info.ring_size),
+        "ring_wptr": int(info.ring_wptr),
+        "sections": {C.SEC_NAMES[s.id]: (int(s.offset), int(s.bytes)) for s in info.sections[:info.n_sections]},
+    }
+    return out
+
+
+def inspect_state(path) -> dict:
+    """inspect_state_blob of a file written by LearnEngine.save_state."""
+    with open(path, "rb") as f:
+        return inspect_state_blob(f.read())
 
 
 def raise_device_error(err: int):
