@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define DQNX_ABI_VERSION 4
+#define DQNX_ABI_VERSION 5
 
 /* ---- status codes ---------------------------------------------------------------- */
 #define DQNX_OK 0
@@ -187,6 +187,8 @@ enum dqnx_buffer {
     DQNX_BUF_PER_ABS_TD,       /* [batch] fp32 |targets - q(s,a)| of the GLOBAL minibatch (PER only):
                                   each rank's learn step writes its shard; under DP the caller
                                   all-gathers it in place before dqnx_apply_grads */
+    DQNX_BUF_LEARN_STATS,      /* one dqnx_learn_stats (ABI 5): accumulated by DQNX_STEP_STATS steps; not
+                                  training state (never in the state blob) */
     DQNX_BUF_COUNT
 };
 int dqnx_engine_buffer(const dqnx_engine* e, int32_t which, uint64_t* offset, uint64_t* bytes);
@@ -291,6 +293,11 @@ int dqnx_rng_advance(const uint32_t* state625, int64_t words, uint32_t* out625);
                                        dqnx_rng_set return DQNX_ESTATE and dqnx_rng_get already
                                        reflects the prefetched draw.  A step without the flag
                                        consumes the pending minibatch. */
+#define DQNX_STEP_STATS 0x10        /* (ABI 5) accumulate this step's training statistics into
+                                       DQNX_BUF_LEARN_STATS: one more launch, "learn_stats", the step's
+                                       last; it only reads the step's buffers, so every other result of
+                                       the step is bitwise what it is without the flag.  See "training
+                                       statistics" below for the fields and where the flag is refused. */
 int dqnx_learn_step(dqnx_engine* e, int32_t flags, void* stream);
 /* Same-stream rule for DQNX_STEP_PREFETCH: the engine remembers the stream of the step that
  * left a draw pending; dqnx_rng_get synchronises THAT stream, and a later step on another
@@ -504,6 +511,68 @@ int dqnx_state_load(dqnx_engine* e, const void* src_host, uint64_t bytes, void* 
 /* Validate a blob (all of the rules above) and copy its header out (host only: no engine, no GPU).
  * DQNX_EINVAL with a message naming what is wrong. */
 int dqnx_state_inspect(const void* blob, uint64_t bytes, dqnx_state_info* out);
+
+/* ---- training statistics (ABI 5): what a learn step computed, accumulated on the device ------
+ * A step with DQNX_STEP_STATS ends with one more launch ("learn_stats" in dqnx_learn_kernel_info) that
+ * reduces the step's own buffers -- DQNX_BUF_Q, DQNX_BUF_TD, DQNX_BUF_GRADS, DQNX_BUF_IS_WEIGHTS, the
+ * online parameters after the step's Adam, dqnx_ctrl.loss, and the replay action / reward / done of the
+ * rows the step sampled -- into the one dqnx_learn_stats of DQNX_BUF_LEARN_STATS.  The block accumulates
+ * over steps; the host reads it once per log window (dqnx_learn_stats_get), not once per step.
+ * Accepted by dqnx_learn_step, dqnx_learn_steps, dqnx_agent_launch, dqnx_agent_learn_mt,
+ * dqnx_learn_step_timed, dqnx_learn_step_omit, dqnx_learn_kernel_count and dqnx_learn_kernel_info.
+ * DQNX_EUNSUPPORTED (the block untouched): together with DQNX_STEP_GRADS_ONLY, in
+ * dqnx_learn_step_bucket / dqnx_apply_grads / dqnx_apply_grads_bucket, on an engine with world_size > 1
+ * (the batch part would need a cross-rank reduction), and for a net of more than
+ * DQNX_STATS_MAX_ACTIONS actions or DQNX_STATS_MAX_TENSORS parameter tensors.
+ * The micro-CNN plan does not draw a minibatch ahead in a DQNX_STEP_STATS step (DQNX_STEP_PREFETCH is
+ * ignored there and dqnx_learn_steps runs the steps one by one): its in-launch draw overwrites the
+ * step's indices before the statistics launch could read them.  Results are the same either way.
+ *
+ * Every sum is carried in fp64 from the first add (an fp32 x fp32 product is exact in fp64) and summed
+ * in an order fixed by the launch geometry, never by scheduling: two runs of the same steps leave the
+ * same bytes.  All fields are over the B rows of a step's minibatch and accumulate over steps, except
+ * the *_last arrays (the last step only).  The first step accumulated into a zeroed block (steps == 0)
+ * SETS the min / max fields, so an all-zero block is the valid empty state.
+ * Not training state: zeroed by dqnx_engine_reset, dqnx_state_load and dqnx_learn_stats_reset, never
+ * written to the state blob. */
+#define DQNX_STATS_MAX_ACTIONS 16
+#define DQNX_STATS_TD_BINS 16
+#define DQNX_STATS_MAX_TENSORS 32
+typedef struct dqnx_learn_stats {
+    int64_t steps;             /* steps accumulated */
+    int64_t rows;              /* sum of B */
+    double q_sa_sum, q_sa_sq_sum;   /* Q(s,a) of the taken action (DQNX_BUF_TD[1]) */
+    double q_max_sum;          /* max_a Q_online(s) (rows of DQNX_BUF_Q[0]) */
+    double target_sum;         /* TD target y (DQNX_BUF_TD[0]) */
+    double abs_td_sum;         /* |delta| (DQNX_BUF_TD[2]) */
+    double gap_sum;            /* top-1 minus top-2 of the DQNX_BUF_Q[0] row, subtracted in fp32 (0 when A = 1) */
+    double reward_sum;         /* replay reward of the sampled rows */
+    double isw_sum;            /* PER importance weights (0 for uniform replay) */
+    double loss_sum;           /* sum of dqnx_ctrl.loss */
+    double grad_norm_sum;      /* sum over steps of sqrt(sum_t grad_sq of the step) */
+    double grad_norm_max;      /* its maximum (a derived fp64 value, so kept in fp64) */
+    int64_t huber_linear_rows; /* rows with |delta| >= 1 (SmoothL1's linear regime, beta = 1) */
+    int64_t agree_rows;        /* rows whose greedy action is the replay action */
+    int64_t done_rows;         /* sampled rows with done != 0 */
+    /* |delta| by fp32 exponent: bin = clamp(e + 12, 0, 15), e the unbiased exponent; 0 and denormals in bin 0 */
+    int64_t td_hist[DQNX_STATS_TD_BINS];
+    int64_t greedy_hist[DQNX_STATS_MAX_ACTIONS];   /* argmax of the DQNX_BUF_Q[0] row, first maximal index */
+    int64_t taken_hist[DQNX_STATS_MAX_ACTIONS];    /* replay action of each sampled row */
+    /* per parameter tensor, dqnx_net_param_info order */
+    double grad_sq_last[DQNX_STATS_MAX_TENSORS];   /* sum g^2 over the tensor, last step */
+    double param_sq_last[DQNX_STATS_MAX_TENSORS];  /* sum theta^2 of the online params after the last step's Adam */
+    double grad_sq_sum[DQNX_STATS_MAX_TENSORS];    /* grad_sq_last accumulated over steps */
+    /* extrema of fp32 buffer values */
+    float q_sa_min, q_sa_max, q_max_max, target_min, target_max, abs_td_max;
+    float isw_min;             /* PER only (0 for uniform replay) */
+    float reserved0;           /* 0 */
+} dqnx_learn_stats;
+/* Copy the block to host memory: synchronises `stream`, and with reset != 0 zeroes the block afterwards
+ * (stream-ordered).  DQNX_ESTATE under dqnx_state_save's pending conditions (a prefetched minibatch, an
+ * unread agent readback, a staged RNG state, between buckets). */
+int dqnx_learn_stats_get(dqnx_engine* e, dqnx_learn_stats* out_host, int32_t reset, void* stream);
+/* Zero the block; stream-ordered, no synchronisation. */
+int dqnx_learn_stats_reset(dqnx_engine* e, void* stream);
 
 /* ---- kernel-level timing (bench.py roofline) ---------------------------------------
  * A learn step is an ordered list of kernel launches (sample, linear_fwd_l1.., head_td_loss,

@@ -442,6 +442,9 @@ struct dqnx_engine {
     int micro_lds_d[MICRO_MAX_CONV] = {0, 0, 0};
     MicroDwArgs micro_dw;
     int stage_rows = 0;
+    // DQNX_STEP_STATS (stats.hip): partials + ticket in the workspace; the launch geometry
+    uint64_t ws_stats_part = 0, ws_stats_ticket = 0;
+    int stats_bwg = 0, stats_rows = 0, stats_chunk = 0, stats_chunks = 0;   // stats_chunks == 0: unsupported net
     char* arena = nullptr;
     int64_t ring_size = 0, ring_wptr = 0;   // host mirror of the ring state (pushes are host-driven)
     bool graphs = false;   // eager launches by default (dqnx_engine_set_graphs)
@@ -642,8 +645,30 @@ int layout(dqnx_engine* e) {
         if (e->f1_ksplit) e->ws_fpart = sub((uint64_t)e->f1_ksplit * 3 * e->Bl * np.dense[0].out * 4);
         if (dcol_max) e->ws_dcol = sub(dcol_max);
     }
+    // learn statistics (DQNX_STEP_STATS): 256 rows per batch workgroup (at most 64 workgroups); the flat
+    // vectors in per-tensor chunks of 8192 elements (32 KiB of each vector per workgroup), doubled until
+    // at most 1024 of them
+    e->stats_rows = std::max(256, (int)align_up((uint64_t)(e->Bl + 63) / 64, 256));
+    e->stats_bwg = (e->Bl + e->stats_rows - 1) / e->stats_rows;
+    e->stats_chunk = 0;
+    e->stats_chunks = 0;
+    if ((int)np.params.size() <= DQNX_STATS_MAX_TENSORS && A <= DQNX_STATS_MAX_ACTIONS) {
+        for (int chunk = 8192;; chunk *= 2) {
+            int64_t n = 0;
+            for (const dqnx_param_info& pi : np.params) n += (pi.numel + chunk - 1) / chunk;
+            if (n <= 1024) {
+                e->stats_chunk = chunk;
+                e->stats_chunks = (int)n;
+                break;
+            }
+        }
+    }
+    e->ws_stats_part = sub(stats_part_bytes(e->stats_bwg, e->stats_chunks));
+    e->ws_stats_ticket = sub(64);
     cur = align_up(cur, 256);
     e->bytes[DQNX_BUF_WORKSPACE] = cur - e->off[DQNX_BUF_WORKSPACE];
+    region(DQNX_BUF_LEARN_STATS, sizeof(dqnx_learn_stats));   // after the workspace: every earlier offset stays
+    cur = align_up(cur, 256);
     e->total = cur;
     return DQNX_OK;
 }
@@ -1464,12 +1489,88 @@ bool inlaunch_prefetch_ok(const dqnx_engine* e, int flags) {
     if (tuning_flag("DQNX_PF_SIDE")) return false;   // measurements: the side-stream pipeline instead
     if (e->cfg.algo == DQNX_ALGO_PER_DOUBLE || (flags & DQNX_STEP_GIVEN_INDICES)) return false;
     if (e->bwd_plan == 2) return e->Bs <= FWD_SAMPLE_MAX_K;
-    return e->bwd_plan == 0 && e->micro && e->Bs <= MICRO_SAMPLE_MAX_K;
+    // (a DQNX_STEP_STATS step of the micro-CNN plan draws nothing ahead: the launch that hosts the draw
+    // also copies it over the step's (idx, phys) slot, which the statistics launch has yet to read)
+    return e->bwd_plan == 0 && e->micro && e->Bs <= MICRO_SAMPLE_MAX_K && !(flags & DQNX_STEP_STATS);
 }
 // the fused plan's blocked weight copies need a rebuild launch before the next step
 static bool relayout_due(const dqnx_engine* e) { return e->bwd_plan == 2 && e->wblk_dirty; }
 
+// DQNX_STEP_STATS where the engine has no statistics launch for the step (include/dqnx.h)
+int stats_refused(const dqnx_engine* e, int flags) {
+    if (!(flags & DQNX_STEP_STATS)) return DQNX_OK;
+    if (flags & DQNX_STEP_GRADS_ONLY)
+        return set_error(DQNX_EUNSUPPORTED, "DQNX_STEP_STATS with DQNX_STEP_GRADS_ONLY is out of scope: the statistics "
+                                            "read the parameters after the step's Adam");
+    if (e->cfg.world_size > 1)
+        return set_error(DQNX_EUNSUPPORTED, "DQNX_STEP_STATS on a world_size %d engine is out of scope: data-parallel "
+                                            "statistics need a cross-rank reduction of the batch part", e->cfg.world_size);
+    if (!e->stats_chunks)
+        return set_error(DQNX_EUNSUPPORTED, "DQNX_STEP_STATS: a net of %d parameter tensors / %d actions (at most %d / %d)",
+                         (int)e->np.params.size(), e->cfg.net.n_actions, DQNX_STATS_MAX_TENSORS, DQNX_STATS_MAX_ACTIONS);
+    return DQNX_OK;
+}
+
+// The statistics launch of a DQNX_STEP_STATS step (stats.hip), its last.  The sampled transitions: the
+// fused plan's forward gathered {act, rew, done} of the step's rows into ws_trans (still this step's
+// when the step's last compute launch has already copied the NEXT minibatch over the index slot, as
+// the in-launch prefetch does); the other plans' rows are read from the ring through the physical
+// slots of the step's own (idx, phys) pair.
+static KStep stats_kstep(dqnx_engine* e, int key) {
+    const dqnx_config& c = e->cfg;
+    const NetPlan& np = e->np;
+    const int slot = (key >> 8) & 1;
+    StatsArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.out = at<dqnx_learn_stats>(e, e->off[DQNX_BUF_LEARN_STATS]);
+    sa.part = at<double>(e, e->ws_stats_part);
+    sa.ticket = at<uint32_t>(e, e->ws_stats_ticket);
+    sa.grads = at<float>(e, e->off[DQNX_BUF_GRADS]);
+    sa.params = at<float>(e, e->off[DQNX_BUF_PARAMS]);
+    sa.n_tensors = (int)np.params.size();
+    sa.chunk = e->stats_chunk;
+    sa.n_chunks = e->stats_chunks;
+    for (int t = 0; t < sa.n_tensors && t < DQNX_STATS_MAX_TENSORS; t++) {
+        sa.t_off[t] = np.params[t].offset;
+        sa.t_off[t + 1] = np.params[t].offset + np.params[t].numel;
+        sa.c0[t + 1] = sa.c0[t] + (int32_t)((np.params[t].numel + sa.chunk - 1) / sa.chunk);
+    }
+    sa.B = e->Bl;
+    sa.A = c.net.n_actions;
+    sa.n_bwg = e->stats_bwg;
+    sa.rows_per_bwg = e->stats_rows;
+    sa.q = at<float>(e, e->off[DQNX_BUF_Q]);
+    sa.td = at<float>(e, e->off[DQNX_BUF_TD]);
+    sa.isw = c.algo == DQNX_ALGO_PER_DOUBLE ? at<float>(e, e->off[DQNX_BUF_IS_WEIGHTS]) : nullptr;
+    if (e->bwd_plan == 2) {
+        sa.trans = at<float4>(e, e->ws_trans);
+    } else {
+        sa.phys = at<int32_t>(e, e->ws_phys) + (size_t)slot * e->Bl;
+        sa.ring_act = at<int32_t>(e, e->off[DQNX_BUF_RING_ACT]);
+        sa.ring_rew = at<float>(e, e->off[DQNX_BUF_RING_REW]);
+        sa.ring_done = at<float>(e, e->off[DQNX_BUF_RING_DONE]);
+    }
+    sa.capacity = c.capacity;
+    sa.ctrl = ctrl_of(e);
+    KStep k;
+    k.name = "learn_stats";
+    k.flops = 0;
+    // what it reads: the gradient and the parameters, Q(s, .), the three TD rows, the transitions
+    k.bytes = 8.0 * (double)np.P + 4.0 * e->Bl * (sa.A + 3.0 + (sa.isw ? 1.0 : 0.0)) + 16.0 * e->Bl;
+    k.run = [=](hipStream_t s) { return launch_learn_stats(sa, s); };
+    return k;
+}
+
+static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key);
+
+// a step's launches: the compute launches of the plan, then (DQNX_STEP_STATS) the statistics launch
 std::vector<KStep> build_learn_steps(dqnx_engine* e, int key) {
+    std::vector<KStep> ks = build_compute_steps(e, key & ~DQNX_STEP_STATS);
+    if ((key & DQNX_STEP_STATS) && e->stats_chunks) ks.push_back(stats_kstep(e, key));
+    return ks;
+}
+
+static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
     const int flags = key & 0x3f;
     const int slot = (key >> 8) & 1;
     std::vector<KStep> ks;
@@ -2987,7 +3088,7 @@ int dqnx_engine_reset(dqnx_engine* e, void* stream) {
     const int ids[] = {DQNX_BUF_GRADS, DQNX_BUF_ADAM_M, DQNX_BUF_ADAM_V, DQNX_BUF_CTRL, DQNX_BUF_RING_OBS,
                        DQNX_BUF_RING_NEXT_OBS, DQNX_BUF_RING_ACT, DQNX_BUF_RING_REW, DQNX_BUF_RING_DONE,
                        DQNX_BUF_SUMTREE, DQNX_BUF_BATCH_IDX, DQNX_BUF_Q, DQNX_BUF_TD, DQNX_BUF_IS_WEIGHTS,
-                       DQNX_BUF_WORKSPACE, DQNX_BUF_PER_ABS_TD};
+                       DQNX_BUF_WORKSPACE, DQNX_BUF_PER_ABS_TD, DQNX_BUF_LEARN_STATS};
     for (int id : ids)
         if (e->bytes[id]) DQNX_HIP_CHECK(hipMemsetAsync(e->arena + e->off[id], 0, e->bytes[id], s));
     // SumTree.max/min_priority_index start at capacity - 1 (R:dqn/utils/sum_tree.py:12-13)
@@ -3407,11 +3508,14 @@ int dqnx_learn_step(dqnx_engine* e, int32_t flags, void* stream) {
     // Fused plan: the last launch of step t (k_dw_adam16) hosts step t+1's sampler workgroup
     // (in-launch prefetch, same stream, no events); where it cannot (k past the multi-pass
     // sampler, slab plan), nothing is drawn ahead.  Per-layer plan: a side-stream pipeline.
-    const int base = flags & (DQNX_STEP_SOFT_UPDATE | DQNX_STEP_GIVEN_INDICES | DQNX_STEP_GRADS_ONLY);
+    rc = stats_refused(e, flags);
+    if (rc) return rc;
+    const int base = flags & (DQNX_STEP_SOFT_UPDATE | DQNX_STEP_GIVEN_INDICES | DQNX_STEP_GRADS_ONLY | DQNX_STEP_STATS);
     const bool inl = inlaunch_prefetch_ok(e, base);
     const bool side = side_fused_ok(e, base);
     const bool prefetch = (flags & DQNX_STEP_PREFETCH) && !(flags & DQNX_STEP_GIVEN_INDICES) &&
-                          e->cfg.algo != DQNX_ALGO_PER_DOUBLE && (e->bwd_plan != 2 || inl || side);
+                          e->cfg.algo != DQNX_ALGO_PER_DOUBLE && (e->bwd_plan != 2 || inl || side) &&
+                          !(e->micro && (flags & DQNX_STEP_STATS));   // (inlaunch_prefetch_ok)
     if (e->ring_size < e->Bs && !(flags & DQNX_STEP_GIVEN_INDICES) && !e->pf_valid)
         return set_error(DQNX_EINVAL, "Sample larger than population: %lld < %d", (long long)e->ring_size, e->Bs);
     if (e->pf_valid && (flags & DQNX_STEP_GIVEN_INDICES))
@@ -3473,9 +3577,11 @@ int dqnx_learn_steps(dqnx_engine* e, int32_t flags, int32_t count, void* stream)
     if (rc) return rc;
     if (count < 1 || count > 256) return set_error(DQNX_EINVAL, "learn_steps: count %d not in [1, 256]", count);
     if (flags & (DQNX_STEP_PREFETCH | DQNX_STEP_GIVEN_INDICES | DQNX_STEP_GRADS_ONLY))
-        return set_error(DQNX_EINVAL, "learn_steps: flags may only hold DQNX_STEP_SOFT_UPDATE");
+        return set_error(DQNX_EINVAL, "learn_steps: flags may only hold DQNX_STEP_SOFT_UPDATE and DQNX_STEP_STATS");
+    rc = stats_refused(e, flags);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int base = flags & DQNX_STEP_SOFT_UPDATE;
+    const int base = flags & (DQNX_STEP_SOFT_UPDATE | DQNX_STEP_STATS);
     if (e->pf_valid || !inlaunch_prefetch_ok(e, base)) {
         for (int i = 0; i < count; i++) {
             rc = dqnx_learn_step(e, base, stream);
@@ -3506,7 +3612,7 @@ int dqnx_learn_steps(dqnx_engine* e, int32_t flags, int32_t count, void* stream)
 // in-launch prefetch applies) the steady-state step of a prefetching loop -- no sampler launch,
 // the last launch draws the next minibatch (into slot 1; timing runs leave the state stale).
 static int timing_key(const dqnx_engine* e, int32_t flags) {
-    const int base = flags & 7;
+    const int base = flags & (7 | DQNX_STEP_STATS);
     if ((flags & DQNX_STEP_PREFETCH) && inlaunch_prefetch_ok(e, base)) return base | KEY_SAMPLE_NEXT;
     return base;
 }
@@ -3528,6 +3634,8 @@ int dqnx_learn_kernel_count(dqnx_engine* e, int32_t flags, int32_t* n) {
     int rc = check_bound(e);
     if (rc) return rc;
     if (!n) return set_error(DQNX_EINVAL, "null argument");
+    rc = stats_refused(e, flags);
+    if (rc) return rc;
     *n = (int32_t)steps_for(e, timing_key(e, flags)).size();
     return DQNX_OK;
 }
@@ -3535,6 +3643,8 @@ int dqnx_learn_kernel_count(dqnx_engine* e, int32_t flags, int32_t* n) {
 int dqnx_learn_kernel_info(dqnx_engine* e, int32_t flags, int32_t i, char* name, int32_t name_len, double* flops,
                            double* bytes) {
     int rc = check_bound(e);
+    if (rc) return rc;
+    rc = stats_refused(e, flags);
     if (rc) return rc;
     const std::vector<KStep>& ks = steps_for(e, timing_key(e, flags));
     if (i < 0 || i >= (int32_t)ks.size()) return set_error(DQNX_EINVAL, "kernel index %d out of range", i);
@@ -3549,6 +3659,8 @@ int dqnx_learn_step_timed(dqnx_engine* e, int32_t flags, int32_t kernel_index, v
     int rc = check_bound(e);
     if (rc) return rc;
     if (!ev_start || !ev_stop) return set_error(DQNX_EINVAL, "null event");
+    rc = stats_refused(e, flags);
+    if (rc) return rc;
     if (e->pf_valid) return set_error(DQNX_ESTATE, "timed step with a prefetched minibatch pending");
     if (e->ring_size < e->Bs && !(flags & DQNX_STEP_GIVEN_INDICES))
         return set_error(DQNX_EINVAL, "Sample larger than population: %lld < %d", (long long)e->ring_size, e->Bs);
@@ -3585,6 +3697,8 @@ int dqnx_learn_step_omit(dqnx_engine* e, int32_t flags, int32_t omit_index, void
     int rc = check_bound(e);
     if (rc) return rc;
     if (e->pf_valid) return set_error(DQNX_ESTATE, "timing step with a prefetched minibatch pending");
+    rc = stats_refused(e, flags);
+    if (rc) return rc;
     if (e->ring_size < e->Bs && !(flags & DQNX_STEP_GIVEN_INDICES))
         return set_error(DQNX_EINVAL, "Sample larger than population: %lld < %d", (long long)e->ring_size, e->Bs);
     const int base = timing_key(e, flags);
@@ -3658,6 +3772,9 @@ int dqnx_prefetch_stream(dqnx_engine* e, void* stream) {
 int dqnx_apply_grads(dqnx_engine* e, int32_t flags, void* stream) {
     int rc = check_bound(e);
     if (rc) return rc;
+    if (flags & DQNX_STEP_STATS)
+        return set_error(DQNX_EUNSUPPORTED, "DQNX_STEP_STATS is out of scope for %s: the statistics launch ends a whole "
+                                            "single-GPU learn step", "dqnx_apply_grads");
     // with an in-launch prefetch pending the next step has no sampler launch: this pass writes the
     // fused plan's blocked copies itself (measured 2.4-2.6 us per DP shard step faster than a
     // relayout launch); otherwise the next sampler launch rebuilds them for free
@@ -3768,6 +3885,9 @@ int dqnx_learn_step_bucket(dqnx_engine* e, int32_t flags, int32_t bucket, void* 
     int rc = check_bound(e);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
+    if (flags & DQNX_STEP_STATS)
+        return set_error(DQNX_EUNSUPPORTED, "DQNX_STEP_STATS is out of scope for %s: the statistics launch ends a whole "
+                                            "single-GPU learn step", "dqnx_learn_step_bucket");
     if (flags & DQNX_STEP_GIVEN_INDICES) return set_error(DQNX_EUNSUPPORTED, "bucketed steps sample their own minibatch");
     std::vector<DpBucket> b;
     rc = dp_buckets(e, b);
@@ -3804,6 +3924,9 @@ int dqnx_learn_step_bucket(dqnx_engine* e, int32_t flags, int32_t bucket, void* 
 int dqnx_apply_grads_bucket(dqnx_engine* e, int32_t flags, int32_t bucket, void* stream) {
     int rc = check_bound(e);
     if (rc) return rc;
+    if (flags & DQNX_STEP_STATS)
+        return set_error(DQNX_EUNSUPPORTED, "DQNX_STEP_STATS is out of scope for %s: the statistics launch ends a whole "
+                                            "single-GPU learn step", "dqnx_apply_grads_bucket");
     hipStream_t s = (hipStream_t)stream;
     std::vector<DpBucket> b;
     rc = dp_buckets(e, b);
@@ -4228,7 +4351,7 @@ static int agent_launch_impl(dqnx_engine* e, int32_t flags, void* stream, int* p
         if (e->ag_zc_used) DQNX_HIP_CHECK(hipEventSynchronize(e->ag_ctrl_ev));   // its last reader has run
         memcpy(e->ag_rng_zc, e->ag_rng_pin + 625 * i, 625 * 4);
         e->ag_zc_launch = true;
-        rc = dqnx_learn_step(e, flags & (DQNX_STEP_SOFT_UPDATE | DQNX_STEP_GRADS_ONLY), stream);
+        rc = dqnx_learn_step(e, flags & (DQNX_STEP_SOFT_UPDATE | DQNX_STEP_GRADS_ONLY | DQNX_STEP_STATS), stream);
         e->ag_zc_launch = false;
         if (rc) return rc;
         e->ag_zc_used = true;
@@ -4237,7 +4360,7 @@ static int agent_launch_impl(dqnx_engine* e, int32_t flags, void* stream, int* p
         DQNX_HIP_CHECK(hipMemcpyAsync(dst, e->ag_rng_pin + 625 * i, 625 * 4, hipMemcpyHostToDevice, s));
         DQNX_HIP_CHECK(hipEventRecord(e->ag_rng_ev[i], s));
         e->ag_rng_live[i] = true;
-        rc = dqnx_learn_step(e, flags & (DQNX_STEP_SOFT_UPDATE | DQNX_STEP_GRADS_ONLY), stream);
+        rc = dqnx_learn_step(e, flags & (DQNX_STEP_SOFT_UPDATE | DQNX_STEP_GRADS_ONLY | DQNX_STEP_STATS), stream);
         if (rc) return rc;
     }
     if (!e->ag_ctrl_pin) {
@@ -4781,6 +4904,8 @@ int dqnx_state_load(dqnx_engine* e, const void* src_host, uint64_t bytes, void* 
     // derived data: the RNG block caches hold successors of the old streams (header word 0 = blocks held)
     DQNX_HIP_CHECK(hipMemsetAsync(e->arena + e->ws_mtc, 0, 256, s));
     if (e->ws_npc) DQNX_HIP_CHECK(hipMemsetAsync(e->arena + e->ws_npc, 0, 256, s));
+    // the learn statistics are a log window's, not the run's: a restored run starts an empty one
+    DQNX_HIP_CHECK(hipMemsetAsync(e->arena + e->off[DQNX_BUF_LEARN_STATS], 0, e->bytes[DQNX_BUF_LEARN_STATS], s));
     if (e->stride16 && n > 0) {   // a bf16 engine gathers the bf16 copies of the rows
         Ring16Args ra;
         memset(&ra, 0, sizeof(ra));
@@ -4810,6 +4935,27 @@ int dqnx_state_load(dqnx_engine* e, const void* src_host, uint64_t bytes, void* 
     return DQNX_OK;
 }
 #undef DQNX_STATE_MATCH
+
+int dqnx_learn_stats_reset(dqnx_engine* e, void* stream) {
+    int rc = check_bound(e);
+    if (rc) return rc;
+    DQNX_HIP_CHECK(hipMemsetAsync(e->arena + e->off[DQNX_BUF_LEARN_STATS], 0, e->bytes[DQNX_BUF_LEARN_STATS],
+                                  (hipStream_t)stream));
+    return DQNX_OK;
+}
+
+int dqnx_learn_stats_get(dqnx_engine* e, dqnx_learn_stats* out_host, int32_t reset, void* stream) {
+    int rc = check_bound(e);
+    if (rc) return rc;
+    if (!out_host) return set_error(DQNX_EINVAL, "null argument");
+    rc = state_pending(e, "learn stats read");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DQNX_HIP_CHECK(hipMemcpyAsync(out_host, e->arena + e->off[DQNX_BUF_LEARN_STATS], sizeof(dqnx_learn_stats),
+                                  hipMemcpyDeviceToHost, s));
+    DQNX_HIP_CHECK(hipStreamSynchronize(s));
+    return reset ? dqnx_learn_stats_reset(e, stream) : (int)DQNX_OK;
+}
 
 int dqnx_debug_stamps(dqnx_engine* e, int64_t* out64, void* stream) {
 #ifdef DQNX_STAMPS

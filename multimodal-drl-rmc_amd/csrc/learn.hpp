@@ -846,6 +846,36 @@ struct Ring16Args {
 };
 int launch_ring16_rebuild(const Ring16Args& a, hipStream_t s);
 
+// DQNX_STEP_STATS (stats.hip): the step's last launch, k_learn_stats.  Workgroups [0, n_bwg) take the
+// minibatch rows, workgroups [n_bwg, n_bwg + n_chunks) one chunk each of the flat gradient / parameter
+// vectors; no chunk crosses a tensor (tensor t owns chunks [c0[t], c0[t + 1]) of `chunk` elements, the
+// last one shorter), so the per-tensor sums are sums of whole chunk partials.
+constexpr int kStatsThreads = 256;
+constexpr int kStatsBatchDoubles = 16;   // doubles of one batch workgroup's partial (stats.hip)
+struct StatsArgs {
+    dqnx_learn_stats* out;
+    double* part;                // workspace: [n_bwg][kStatsBatchDoubles], then [n_chunks][2]
+    uint32_t* ticket;            // arrival counter, zero between launches
+    const float* grads;          // [P]
+    const float* params;         // [P] online parameters (after the step's Adam)
+    int n_tensors, n_chunks, chunk;
+    int64_t t_off[DQNX_STATS_MAX_TENSORS + 1];   // element offsets; t_off[n_tensors] = P
+    int32_t c0[DQNX_STATS_MAX_TENSORS + 1];
+    int B, A, n_bwg, rows_per_bwg;
+    const float* q;              // DQNX_BUF_Q stream 0: [B][A]
+    const float* td;             // DQNX_BUF_TD: [3][B]
+    const float* isw;            // [B] PER importance weights, or null
+    const float4* trans;         // fused plan: [B] {act, rew, done, 0} the step's forward gathered, or null:
+    const int32_t* phys;         //   [B] ring slots the step gathered from, into the ring columns below
+    const int32_t* ring_act;
+    const float* ring_rew;
+    const float* ring_done;
+    int64_t capacity;
+    const dqnx_ctrl* ctrl;       // loss
+};
+uint64_t stats_part_bytes(int n_bwg, int n_chunks);
+int launch_learn_stats(const StatsArgs& a, hipStream_t s);
+
 int launch_sample_uniform(const SampleArgs& a, hipStream_t s);
 int launch_idx_to_phys(const int32_t* idx, int32_t* phys, int shard_begin, int n, dqnx_ctrl* ctrl, int64_t capacity,
                        const RelayoutArgs* rl, int rl_blocks, hipStream_t s);

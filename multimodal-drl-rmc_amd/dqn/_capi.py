@@ -25,12 +25,13 @@ DQNX_ALGO_DQN, DQNX_ALGO_DOUBLE, DQNX_ALGO_PER_DOUBLE = 0, 1, 2
 DQNX_MAX_DENSE, DQNX_MAX_CONV = 6, 4
 (BUF_PARAMS, BUF_TARGET_PARAMS, BUF_GRADS, BUF_ADAM_M, BUF_ADAM_V, BUF_CTRL, BUF_RING_OBS,
  BUF_RING_NEXT_OBS, BUF_RING_ACT, BUF_RING_REW, BUF_RING_DONE, BUF_SUMTREE, BUF_BATCH_IDX, BUF_Q,
- BUF_TD, BUF_IS_WEIGHTS, BUF_WORKSPACE, BUF_PER_ABS_TD, BUF_COUNT) = range(19)
+ BUF_TD, BUF_IS_WEIGHTS, BUF_WORKSPACE, BUF_PER_ABS_TD, BUF_LEARN_STATS, BUF_COUNT) = range(20)
 DQNX_RNG_PY, DQNX_RNG_NP = 0, 1
 STEP_SOFT_UPDATE = 0x1
 STEP_GIVEN_INDICES = 0x2
 STEP_GRADS_ONLY = 0x4
 STEP_PREFETCH = 0x8
+STEP_STATS = 0x10      # accumulate the step's training statistics (dqnx_learn_stats)
 AGENT_LAUNCH = 0x100   # dqnx_agent_learn_mt: launch in the same call
 CHOOSE_MAX_ENVS = 256
 CHOOSE_GIL_HELD = 0x1
@@ -82,6 +83,27 @@ class Ctrl(ctypes.Structure):
     ]
 
 
+# training statistics (dqnx.h "training statistics")
+STATS_MAX_ACTIONS, STATS_TD_BINS, STATS_MAX_TENSORS = 16, 16, 32
+
+
+class LearnStats(ctypes.Structure):
+    _fields_ = [
+        ("steps", I64), ("rows", I64), ("q_sa_sum", ctypes.c_double), ("q_sa_sq_sum", ctypes.c_double),
+        ("q_max_sum", ctypes.c_double), ("target_sum", ctypes.c_double), ("abs_td_sum", ctypes.c_double),
+        ("gap_sum", ctypes.c_double), ("reward_sum", ctypes.c_double), ("isw_sum", ctypes.c_double),
+        ("loss_sum", ctypes.c_double), ("grad_norm_sum", ctypes.c_double), ("grad_norm_max", ctypes.c_double),
+        ("huber_linear_rows", I64), ("agree_rows", I64), ("done_rows", I64),
+        ("td_hist", I64 * STATS_TD_BINS), ("greedy_hist", I64 * STATS_MAX_ACTIONS),
+        ("taken_hist", I64 * STATS_MAX_ACTIONS),
+        ("grad_sq_last", ctypes.c_double * STATS_MAX_TENSORS), ("param_sq_last", ctypes.c_double * STATS_MAX_TENSORS),
+        ("grad_sq_sum", ctypes.c_double * STATS_MAX_TENSORS),
+        ("q_sa_min", ctypes.c_float), ("q_sa_max", ctypes.c_float), ("q_max_max", ctypes.c_float),
+        ("target_min", ctypes.c_float), ("target_max", ctypes.c_float), ("abs_td_max", ctypes.c_float),
+        ("isw_min", ctypes.c_float), ("reserved0", ctypes.c_float),
+    ]
+
+
 # training-state snapshot (dqnx.h "training-state snapshot")
 STATE_MAGIC = 0x54415453584E5144   # b"DQNXSTAT" little-endian
 STATE_VERSION = 1
@@ -123,6 +145,7 @@ EXPORTS = [
     "dqnx_agent_stage_rng", "dqnx_agent_launch", "dqnx_agent_readback", "dqnx_act_host_scratch_bytes",
     "dqnx_act_host", "dqnx_agent_learn_mt", "dqnx_agent_quiesce", "dqnx_agent_choose", "dqnx_act_kernel_count",
     "dqnx_state_bytes", "dqnx_state_save", "dqnx_state_load", "dqnx_state_inspect",
+    "dqnx_learn_stats_get", "dqnx_learn_stats_reset",
 ]
 
 GIL_HELD = ("dqnx_agent_learn_mt", "dqnx_agent_choose")   # entry points called with the GIL held (see lib())
@@ -208,6 +231,8 @@ def lib():
         "dqnx_state_save": ([vp, vp, ctypes.c_uint64, P(ctypes.c_uint64), vp], ctypes.c_int),
         "dqnx_state_load": ([vp, vp, ctypes.c_uint64, vp], ctypes.c_int),
         "dqnx_state_inspect": ([vp, ctypes.c_uint64, P(StateInfo)], ctypes.c_int),
+        "dqnx_learn_stats_get": ([vp, P(LearnStats), I32, vp], ctypes.c_int),
+        "dqnx_learn_stats_reset": ([vp, vp], ctypes.c_int),
     }
     # dqnx_agent_learn_mt reads and writes random._inst's MT words in place: call it through a PyDLL
     # handle, which keeps the GIL for the call (a CDLL call releases it, and another thread's `random`

@@ -70,6 +70,12 @@ def _train_state_on() -> bool:
     return os.environ.get("DQNX_TRAIN_STATE", "0") not in ("", "0")
 
 
+def _learn_stats_on() -> bool:
+    """DQNX_LEARN_STATS=1: every learn step also accumulates the training statistics on the device
+    (DQNX_STEP_STATS) and log() writes them as scalars, so an unmodified train.py gets them."""
+    return os.environ.get("DQNX_LEARN_STATS", "0") not in ("", "0")
+
+
 def _summary_writer(log_dir):
     try:
         from torch.utils.tensorboard import SummaryWriter
@@ -244,6 +250,7 @@ class Agent:
         self._learn_pending = False    # learn() recorded, not launched yet (DQNX_AGENT_DEFER=1)
         if os.environ.get("DQNX_AGENT_GRAPHS", "0") == "1":   # each learn step as one graph launch
             self.engine.set_graphs(True)
+        self.engine.collect_stats = _learn_stats_on()
         self.engine.launch_hook = self._launch_pending
         self.engine.settle_hook = self.flush
         self.update_target_network(force=True)
@@ -541,6 +548,40 @@ class Agent:
                 self.save_training_state(self.save_path + '.state')
             print("OK!")
 
+    @property
+    def collect_learn_stats(self) -> bool:
+        """Learn steps accumulate the training statistics and log() writes them (off by default;
+        DQNX_LEARN_STATS=1 turns it on at construction)."""
+        return self.engine.collect_stats
+
+    @collect_learn_stats.setter
+    def collect_learn_stats(self, on):
+        self._launch_pending()   # a recorded step keeps the setting it was recorded under
+        self.engine.collect_stats = bool(on)
+
+    def _log_learn_stats(self, step):
+        """The scalars of the log window's training statistics (one blocking read, then the block is
+        zeroed for the next window); returns the window's mean loss, or None for an empty window."""
+        st = self.engine.learn_stats(reset=True)
+        if st["steps"] == 0:
+            return None
+        add = self.summary_writer.add_scalar
+        add('QMean', st["q_sa_mean"], global_step=step)
+        add('QMaxMean', st["q_max_mean"], global_step=step)
+        add('TargetMean', st["target_mean"], global_step=step)
+        add('TDAbsMean', st["abs_td_mean"], global_step=step)
+        add('TDAbsMax', st["abs_td_max"], global_step=step)
+        add('HuberLinearFrac', st["huber_linear_frac"], global_step=step)
+        add('ActionGap', st["gap_mean"], global_step=step)
+        p = st["greedy_hist"] / max(int(st["greedy_hist"].sum()), 1)
+        add('GreedyActionEntropy', float(-(p[p > 0] * np.log(p[p > 0])).sum()), global_step=step)
+        add('GradNorm', st["grad_norm_mean"], global_step=step)
+        for name, g in st["grad_norm_last"].items():
+            add('GradNorm/' + name, g, global_step=step)
+        if self.engine.cfg.algo == C.DQNX_ALGO_PER_DOUBLE:
+            add('ISWeightMean', st["isw_mean"], global_step=step)
+        return st["loss_mean"]
+
     def log(self):
         if self.step % self.log_frequency == 0 and self.step > self.resume_step:
             self.flush()
@@ -554,7 +595,9 @@ class Agent:
             self.summary_writer.add_scalar('AvgRew', rew_mean, global_step=self.step * self.n_env)
             self.summary_writer.add_scalar('AvgEpLen', len_mean, global_step=self.step * self.n_env)
             self.summary_writer.add_scalar('Episodes', self.episode_count, global_step=self.step * self.n_env)
-            self.summary_writer.add_scalar('Loss', self.engine.loss(), global_step=self.step * self.n_env)
+            loss = self._log_learn_stats(self.step * self.n_env) if self.engine.collect_stats else None
+            self.summary_writer.add_scalar('Loss', self.engine.loss() if loss is None else loss,
+                                           global_step=self.step * self.n_env)
             self.summary_writer.add_scalar('LearnTransitionsPerSec', self.learn_throughput(),
                                            global_step=self.step * self.n_env)
 

@@ -269,6 +269,9 @@ class LearnEngine:
         self.ring_done = self.view(C.BUF_RING_DONE, torch.float32)
         self.sumtree = self.view(C.BUF_SUMTREE, torch.float64)      # [2*cap-1] (PER), else empty
         self.per_abs_td = self.view(C.BUF_PER_ABS_TD, torch.float32)  # [batch] (PER), else empty
+        self.learn_stats_view = self.view(C.BUF_LEARN_STATS, torch.uint8)   # one dqnx_learn_stats (C.LearnStats)
+        # agent_launch / agent_learn_mt steps also accumulate the training statistics (DQNX_STEP_STATS)
+        self.collect_stats = False
         self.ring_size = 0
         self.ring_wptr = 0
         self.agent_step = 0      # host mirror of dqnx_ctrl.agent_step (PER beta schedule)
@@ -414,8 +417,8 @@ class LearnEngine:
         return int(w.value)
 
     def agent_launch(self, soft_update: bool = False) -> None:
-        C.check(self.L.dqnx_agent_launch(self.h, C.STEP_SOFT_UPDATE if soft_update else 0, self.stream()),
-                "agent_launch")
+        flags = (C.STEP_SOFT_UPDATE if soft_update else 0) | (C.STEP_STATS if self.collect_stats else 0)
+        C.check(self.L.dqnx_agent_launch(self.h, flags, self.stream()), "agent_launch")
         self._ag_unread = True
         if self.cfg.algo == C.DQNX_ALGO_PER_DOUBLE:   # every PER learn step samples: step += n_env
             self.agent_step += self.cfg.n_env
@@ -425,7 +428,8 @@ class LearnEngine:
         device draw, advance it in place past the words the draw consumes, and (launch) launch the step
         as agent_launch does.  Returns the words consumed."""
         w = C.I64()
-        flags = (C.AGENT_LAUNCH if launch else 0) | (C.STEP_SOFT_UPDATE if soft_update else 0)
+        flags = (C.AGENT_LAUNCH if launch else 0) | (C.STEP_SOFT_UPDATE if soft_update else 0) \
+            | (C.STEP_STATS if self.collect_stats else 0)
         if launch and self._ag_unread:
             # the previous step's control block is still unread: wait for it here, through the CDLL
             # binding (GIL released), not inside dqnx_agent_learn_mt (GIL held for random._inst)
@@ -475,11 +479,14 @@ class LearnEngine:
         one (e.g. into a caller's own stream capture)."""
         C.check(self.L.dqnx_engine_set_graphs(self.h, 1 if on else 0), "set_graphs")
 
-    def learn_step(self, soft_update=False, given_indices=False, grads_only=False, prefetch=False):
+    def learn_step(self, soft_update=False, given_indices=False, grads_only=False, prefetch=False, stats=False):
         """One learn step (+ fused soft update).  prefetch=True also draws the next step's
-        minibatch on a forked graph branch (pure learning loops; see DQNX_STEP_PREFETCH)."""
+        minibatch on a forked graph branch (pure learning loops; see DQNX_STEP_PREFETCH).
+        stats=True: one more launch accumulates the step's training statistics on the device
+        (DQNX_STEP_STATS; read them with learn_stats())."""
         flags = (C.STEP_SOFT_UPDATE if soft_update else 0) | (C.STEP_GIVEN_INDICES if given_indices else 0) \
-            | (C.STEP_GRADS_ONLY if grads_only else 0) | (C.STEP_PREFETCH if prefetch else 0)
+            | (C.STEP_GRADS_ONLY if grads_only else 0) | (C.STEP_PREFETCH if prefetch else 0) \
+            | (C.STEP_STATS if stats else 0)
         C.check(self.L.dqnx_learn_step(self.h, flags, self.stream()), "learn_step")
         if self.cfg.algo == C.DQNX_ALGO_PER_DOUBLE:   # every PER learn step samples: step += n_env
             self.agent_step += self.cfg.n_env
@@ -489,12 +496,12 @@ class LearnEngine:
         C.check(self.L.dqnx_prefetch_begin(self.h, C.STEP_GRADS_ONLY if grads_only else 0, self.stream()),
                 "prefetch_begin")
 
-    def learn_steps(self, count: int, soft_update=False):
+    def learn_steps(self, count: int, soft_update=False, stats=False):
         """`count` consecutive learn steps in one call (dqnx_learn_steps): bitwise equal to
-        `count` learn_step(soft_update) calls; one graph on the fused MLP plan, with every step's
-        minibatch after the first drawn inside the previous step's last launch."""
-        C.check(self.L.dqnx_learn_steps(self.h, C.STEP_SOFT_UPDATE if soft_update else 0, int(count),
-                                        self.stream()), "learn_steps")
+        `count` learn_step(soft_update, stats=stats) calls; one graph on the fused MLP plan, with every
+        step's minibatch after the first drawn inside the previous step's last launch."""
+        flags = (C.STEP_SOFT_UPDATE if soft_update else 0) | (C.STEP_STATS if stats else 0)
+        C.check(self.L.dqnx_learn_steps(self.h, flags, int(count), self.stream()), "learn_steps")
         if self.cfg.algo == C.DQNX_ALGO_PER_DOUBLE:
             self.agent_step += self.cfg.n_env * int(count)
 
@@ -571,6 +578,57 @@ class LearnEngine:
     def set_agent_step(self, step_times_n_env: int):
         C.check(self.L.dqnx_set_agent_step(self.h, int(step_times_n_env), self.stream()), "set_agent_step")
         self.agent_step = int(step_times_n_env)
+
+    # ---- training statistics (dqnx_learn_stats_*: include/dqnx.h "training statistics") -------------
+    def learn_stats_raw(self, reset=False) -> C.LearnStats:
+        """The dqnx_learn_stats block as it lies on the device (dqnx_learn_stats_get: synchronises the
+        stream; reset=True zeroes the block afterwards)."""
+        self.settle()   # a drop-in Agent's recorded step is launched and its readback consumed first
+        out = C.LearnStats()
+        C.check(self.L.dqnx_learn_stats_get(self.h, ctypes.byref(out), 1 if reset else 0, self.stream()),
+                "learn_stats_get")
+        return out
+
+    def learn_stats_reset(self):
+        """Zero the statistics block (stream-ordered, no synchronisation)."""
+        C.check(self.L.dqnx_learn_stats_reset(self.h, self.stream()), "learn_stats_reset")
+
+    def learn_stats(self, reset=False) -> dict:
+        """The statistics the stats=True steps since the last reset accumulated: ONE blocking read, meant
+        for log cadence.  The raw dqnx_learn_stats fields (arrays as numpy arrays cut to the net's
+        actions / tensors), the window means derived from them, and per tensor -- keyed by the
+        state_dict names -- grad_norm_last / param_norm_last of the last step.  Means of an empty
+        window (steps == 0) are 0."""
+        st = self.learn_stats_raw(reset)
+        A, nt = self.spec.n_actions, len(self.param_layout)
+        cut = {"td_hist": C.STATS_TD_BINS, "greedy_hist": A, "taken_hist": A, "grad_sq_last": nt,
+               "param_sq_last": nt, "grad_sq_sum": nt}
+        d = {}
+        for name, ctype in C.LearnStats._fields_:
+            if name == "reserved0":
+                continue
+            v = getattr(st, name)
+            if name in cut:
+                d[name] = np.array(v[:cut[name]], dtype=np.int64 if name.endswith("hist") else np.float64)
+            else:
+                d[name] = float(v) if ctype in (ctypes.c_double, ctypes.c_float) else int(v)
+        rows, steps = max(d["rows"], 1), max(d["steps"], 1)
+        d["q_sa_mean"] = d["q_sa_sum"] / rows
+        d["q_sa_std"] = float(np.sqrt(max(d["q_sa_sq_sum"] / rows - d["q_sa_mean"] ** 2, 0.0)))
+        d["q_max_mean"] = d["q_max_sum"] / rows
+        d["target_mean"] = d["target_sum"] / rows
+        d["abs_td_mean"] = d["abs_td_sum"] / rows
+        d["huber_linear_frac"] = d["huber_linear_rows"] / rows
+        d["gap_mean"] = d["gap_sum"] / rows
+        d["reward_mean"] = d["reward_sum"] / rows
+        d["done_frac"] = d["done_rows"] / rows
+        d["isw_mean"] = d["isw_sum"] / rows
+        d["loss_mean"] = d["loss_sum"] / steps
+        d["grad_norm_mean"] = d["grad_norm_sum"] / steps
+        names = [name for name, _, _ in self.param_layout]
+        d["grad_norm_last"] = {n: float(np.sqrt(g)) for n, g in zip(names, d["grad_sq_last"])}
+        d["param_norm_last"] = {n: float(np.sqrt(p)) for n, p in zip(names, d["param_sq_last"])}
+        return d
 
     # ---- training-state snapshot (dqnx_state_*: include/dqnx.h "training-state snapshot") ----------
     def state_bytes(self) -> int:
