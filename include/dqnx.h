@@ -189,6 +189,9 @@ enum dqnx_buffer {
                                   all-gathers it in place before dqnx_apply_grads */
     DQNX_BUF_LEARN_STATS,      /* one dqnx_learn_stats (ABI 5): accumulated by DQNX_STEP_STATS steps; not
                                   training state (never in the state blob) */
+    DQNX_BUF_GRAD_CLIP,        /* one dqnx_grad_clip_info, then the clipping launches' scratch (the step's
+                                  coefficient at byte 64, the sum-of-squares partials from byte 128): written by
+                                  clipped steps only; not training state (never in the state blob) */
     DQNX_BUF_COUNT
 };
 int dqnx_engine_buffer(const dqnx_engine* e, int32_t which, uint64_t* offset, uint64_t* bytes);
@@ -573,6 +576,51 @@ typedef struct dqnx_learn_stats {
 int dqnx_learn_stats_get(dqnx_engine* e, dqnx_learn_stats* out_host, int32_t reset, void* stream);
 /* Zero the block; stream-ordered, no synchronisation. */
 int dqnx_learn_stats_reset(dqnx_engine* e, void* stream);
+
+/* ---- gradient clipping: the global norm of the gradient, clipped on the device before Adam ------
+ * torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) between loss.backward() and
+ * optimizer.step(), where the reference's learn() leaves room for it (R:dqn/agent.py:224-226):
+ *   total_norm = sqrt(sum over every parameter element of g^2)   (the loss slot grads[n_params] is not part)
+ *   coef       = min(max_norm / (total_norm + 1e-6), 1.0)        (fp32: one correctly rounded division;
+ *                torch evaluates float / tensor as tensor.reciprocal() * float, two roundings, so its
+ *                coefficient may differ from this one by 1 ulp)
+ *   g'         = g * coef        one fp32 multiply per element, also when coef == 1
+ * Adam and the fused soft update consume g'.  A non-finite norm is not special-cased (torch's
+ * error_if_nonfinite=False).  max_norm <= 0 means off, the default: a step then launches exactly what it
+ * launches without this section.  DQNX_BUF_GRADS keeps the UNSCALED gradient, and the statistics launch
+ * (grad_norm_*, grad_sq_*) and last_norm report the pre-clip norm: the number max_norm is chosen from.
+ *
+ * While clipping is on, a learn step is the DQNX_STEP_GRADS_ONLY step's launches, then "grad_sumsq" (one
+ * fp64 partial of sum g^2 per workgroup of DQNX_BUF_GRADS[0, n_params), in an order fixed by the launch
+ * geometry, no atomics), "clip_coef" (one workgroup: the partials in index order, the coefficient, the
+ * info block) and dqnx_apply_grads' launch with every gradient element multiplied by the coefficient
+ * (under PER the tree update dqnx_apply_grads makes); then the statistics launch, if asked for.  So a
+ * clipped dqnx_learn_step equals dqnx_learn_step(DQNX_STEP_GRADS_ONLY) + dqnx_apply_grads bit for bit, and
+ * with coef == 1 the unclipped step.  It applies to dqnx_learn_step, dqnx_learn_steps (the steps one by
+ * one), dqnx_agent_launch / dqnx_agent_learn_mt, dqnx_apply_grads (under data parallelism the norm of the
+ * all-reduced gradient: every rank computes the same coefficient from the same bytes) and to what
+ * dqnx_learn_kernel_count / _info / dqnx_learn_step_timed / _omit describe (a dqnx_learn_step_omit step,
+ * as without clipping, leaves the engine fit for timing only).  DQNX_EUNSUPPORTED while
+ * clipping is on: dqnx_learn_step_bucket / dqnx_apply_grads_bucket (a bucket's Adam runs before the last
+ * bucket's gradient exists).
+ *
+ * dqnx_set_grad_clip: host only; max_norm is configuration like lr (not in the state blob).  It drops the
+ *   engine's cached plans and graphs (the value is a launch argument), so a caller's own captured graph of
+ *   engine calls keeps the value it was captured with.  DQNX_ESTATE under dqnx_state_save's pending
+ *   conditions (a prefetched minibatch, an unread agent readback, a staged RNG state, between buckets).
+ * dqnx_grad_clip_info: accumulated on the device by "clip_coef", one plain read-modify-write per clipped
+ *   step; read at log cadence.  Not training state: zeroed by dqnx_engine_reset and dqnx_state_load,
+ *   never written to the state blob.
+ * dqnx_grad_clip_info_get: copies the block to host memory, synchronises `stream`, and with reset != 0
+ *   zeroes it afterwards (stream-ordered).  DQNX_ESTATE as dqnx_learn_stats_get. */
+int dqnx_set_grad_clip(dqnx_engine* e, double max_norm);      /* host only; <= 0 turns it off */
+int dqnx_get_grad_clip(const dqnx_engine* e, double* max_norm);
+typedef struct dqnx_grad_clip_info {
+    int64_t steps, clipped_steps;        /* clipped: coef < 1 */
+    double norm_sum, norm_max;           /* pre-clip total_norm over steps */
+    float last_norm, last_coef;
+} dqnx_grad_clip_info;
+int dqnx_grad_clip_info_get(dqnx_engine* e, dqnx_grad_clip_info* out_host, int32_t reset, void* stream);
 
 /* ---- kernel-level timing (bench.py roofline) ---------------------------------------
  * A learn step is an ordered list of kernel launches (sample, linear_fwd_l1.., head_td_loss,

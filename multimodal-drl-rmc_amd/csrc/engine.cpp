@@ -445,6 +445,10 @@ struct dqnx_engine {
     // DQNX_STEP_STATS (stats.hip): partials + ticket in the workspace; the launch geometry
     uint64_t ws_stats_part = 0, ws_stats_ticket = 0;
     int stats_bwg = 0, stats_rows = 0, stats_chunk = 0, stats_chunks = 0;   // stats_chunks == 0: unsupported net
+    // gradient clipping (clip.hip): max_norm (<= 0: off) and the sum-of-squares launch geometry
+    double grad_clip = 0.0;
+    int64_t clip_chunk = 0;
+    int clip_parts = 0;
     char* arena = nullptr;
     int64_t ring_size = 0, ring_wptr = 0;   // host mirror of the ring state (pushes are host-driven)
     bool graphs = false;   // eager launches by default (dqnx_engine_set_graphs)
@@ -668,6 +672,10 @@ int layout(dqnx_engine* e) {
     cur = align_up(cur, 256);
     e->bytes[DQNX_BUF_WORKSPACE] = cur - e->off[DQNX_BUF_WORKSPACE];
     region(DQNX_BUF_LEARN_STATS, sizeof(dqnx_learn_stats));   // after the workspace: every earlier offset stays
+    // gradient clipping: the info block, the step's coefficient, one fp64 partial per sum-of-squares workgroup
+    static_assert(sizeof(dqnx_grad_clip_info) <= kClipCoefOff && kClipCoefOff + 4 <= kClipPartOff, "clip block");
+    clip_geometry(P, &e->clip_chunk, &e->clip_parts);
+    region(DQNX_BUF_GRAD_CLIP, kClipPartOff + (uint64_t)e->clip_parts * sizeof(double));
     cur = align_up(cur, 256);
     e->total = cur;
     return DQNX_OK;
@@ -1453,6 +1461,13 @@ constexpr int KEY_SAMPLE_NEXT = 0x80;
 // KEY_AGENT_RNG: the sampler launch draws from the drop-in Agent's pinned state block in place
 // (dqnx_agent_launch, uniform replay) instead of the control block an upload copy filled
 constexpr int KEY_AGENT_RNG = 0x4000;
+// KEY_CLIP (gradient clipping on, a whole step): the launches of the DQNX_STEP_GRADS_ONLY plan, then the
+// clipping tail below.  One bit of its own, as DQNX_STEP_STATS is 0x10: no other key changes.
+constexpr int KEY_CLIP = 0x20;
+// KEY_CLIP_TAIL: the launches after the gradient -- grad_sumsq, clip_coef, dqnx_apply_grads' launches with
+// the coefficient (key bits 0x200 / 0x400 as enqueue_apply reads them), then (DQNX_STEP_STATS) the
+// statistics launch on slot (key >> 8) & 1
+constexpr int KEY_CLIP_TAIL = 0x8000;
 
 SampleArgs uniform_sample_args(dqnx_engine* e, int32_t* idx, int32_t* phys) {
     dqnx_ctrl* ctrl = ctrl_of(e);
@@ -1562,9 +1577,85 @@ static KStep stats_kstep(dqnx_engine* e, int key) {
 }
 
 static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key);
+int enqueue_apply(dqnx_engine* e, int flags, hipStream_t s, int parts = 3);
+
+static bool clip_on(const dqnx_engine* e) { return e->grad_clip > 0.0; }
+
+ClipArgs clip_args(dqnx_engine* e) {
+    ClipArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    char* blk = e->arena + e->off[DQNX_BUF_GRAD_CLIP];
+    ca.grads = at<float>(e, e->off[DQNX_BUF_GRADS]);
+    ca.n_params = e->np.P;
+    ca.chunk = e->clip_chunk;
+    ca.n_part = e->clip_parts;
+    ca.part = reinterpret_cast<double*>(blk + kClipPartOff);
+    ca.coef = reinterpret_cast<float*>(blk + kClipCoefOff);
+    ca.info = reinterpret_cast<dqnx_grad_clip_info*>(blk);
+    ca.max_norm = (float)e->grad_clip;   // torch: the Python float max_norm against an fp32 tensor
+    return ca;
+}
+
+// The tail of a clipped step (KEY_CLIP_TAIL), and all of a clipped dqnx_apply_grads: the gradient's sum
+// of squares, the coefficient, then dqnx_apply_grads' launches reading it (clip.hip).
+static std::vector<KStep> clip_tail_steps(dqnx_engine* e, int key) {
+    std::vector<KStep> ks;
+    const double P = (double)e->np.P;
+    const ClipArgs ca = clip_args(e);
+    const int akey = (key & (DQNX_STEP_SOFT_UPDATE | 0x200 | 0x400)) | KEY_CLIP;
+    const bool soft = (key & DQNX_STEP_SOFT_UPDATE) != 0;
+    KStep k;
+    k.name = "grad_sumsq";
+    k.flops = 2.0 * P;
+    k.bytes = 4.0 * P + 8.0 * ca.n_part;
+    k.run = [=](hipStream_t s) { return launch_grad_sumsq(ca, s); };
+    ks.push_back(k);
+    k.name = "clip_coef";
+    k.flops = 0;
+    k.bytes = 8.0 * ca.n_part + sizeof(dqnx_grad_clip_info);
+    k.run = [=](hipStream_t s) { return launch_clip_coef(ca, s); };
+    ks.push_back(k);
+    if (e->cfg.algo == DQNX_ALGO_PER_DOUBLE) {   // the tree update dqnx_apply_grads makes
+        k.name = "per_update";
+        k.flops = 0;
+        k.bytes = 12.0 * e->Bg;
+        k.run = [=](hipStream_t s) { return enqueue_apply(e, akey, s, 1); };
+        ks.push_back(k);
+    }
+    k.name = "adam_clipped";
+    k.flops = 13.0 * P;   // g * coef, then Adam
+    k.bytes = 4.0 * (7.0 * P + (soft ? 2.0 * P : 0.0));   // read g, p, m, v (+ target); write p, m, v (+ target)
+    k.run = [=](hipStream_t s) {
+        const int rc = enqueue_apply(e, akey, s, 2);
+        if (rc) return rc;
+        // dqnx_apply_grads' bookkeeping, here too so that an eagerly enqueued plan (dqnx_learn_step_timed)
+        // leaves it right: mode 2 changes the conv weights without their permuted copies, and the
+        // fused plan's blocked copies are current only if this pass wrote them
+        e->perm_dirty = true;
+        if (akey & 0x200) e->wblk_dirty = false;
+        else if (!adam_keeps_blk(e)) e->wblk_dirty = true;
+        return rc;
+    };
+    ks.push_back(k);
+    if ((key & DQNX_STEP_STATS) && e->stats_chunks) ks.push_back(stats_kstep(e, key));
+    return ks;
+}
 
 // a step's launches: the compute launches of the plan, then (DQNX_STEP_STATS) the statistics launch
 std::vector<KStep> build_learn_steps(dqnx_engine* e, int key) {
+    if (key & KEY_CLIP_TAIL) return clip_tail_steps(e, key);
+    if (key & KEY_CLIP) {
+        // gradient clipping: the gradient-only plan, then the tail.  With the in-launch draw
+        // (KEY_SAMPLE_NEXT) a minibatch is pending when the Adam pass runs: on the fused plan it
+        // writes the blocked copies itself, as dqnx_apply_grads does then
+        std::vector<KStep> ks =
+            build_compute_steps(e, (key & ~(KEY_CLIP | DQNX_STEP_STATS | DQNX_STEP_SOFT_UPDATE)) | DQNX_STEP_GRADS_ONLY);
+        const bool keep = e->bwd_plan == 2 && (key & KEY_SAMPLE_NEXT);
+        const std::vector<KStep> tail = clip_tail_steps(
+            e, KEY_CLIP_TAIL | (key & (DQNX_STEP_SOFT_UPDATE | DQNX_STEP_STATS | 0x100)) | (keep ? 0x600 : 0));
+        ks.insert(ks.end(), tail.begin(), tail.end());
+        return ks;
+    }
     std::vector<KStep> ks = build_compute_steps(e, key & ~DQNX_STEP_STATS);
     if ((key & DQNX_STEP_STATS) && e->stats_chunks) ks.push_back(stats_kstep(e, key));
     return ks;
@@ -2542,7 +2633,9 @@ static DwAdam16Args dw16_subset(const DwAdam16Args& a, uint32_t mask, bool first
         b.L[b.nl++] = d;
     }
     b.tiles = tiles;
-    if (!first) {
+    // (loss_partial shares its slot with the clip coefficient's address, DwAdam16Args::gscale: a clipped
+    // launch keeps it.  No caller passes one today -- the bucketed entry points refuse clipping)
+    if (!first && !a.clip) {
         b.loss_partial = nullptr;
         b.n_loss_partial = 0;
     }
@@ -2556,9 +2649,13 @@ static DwAdam16Args dw16_subset(const DwAdam16Args& a, uint32_t mask, bool first
     return b;
 }
 
-int enqueue_apply(dqnx_engine* e, int flags, hipStream_t s) {
+// flags & KEY_CLIP: the Adam launch multiplies every gradient element by the step's clip coefficient.
+// parts: 1 = the PER priority update's own launches, 2 = the Adam launch (a clipped step's plan lists
+// them as launches of their own)
+int enqueue_apply(dqnx_engine* e, int flags, hipStream_t s, int parts) {
     const bool keep_blk = (flags & 0x200) != 0;   // (a prefetched minibatch is pending: no sampler launch next)
     const dqnx_config& c = e->cfg;
+    const float* gscale = (flags & KEY_CLIP) ? at<float>(e, e->off[DQNX_BUF_GRAD_CLIP] + kClipCoefOff) : nullptr;
     // priorities from the all-gathered |delta| (DP); k_per_prop's workgroups ride in the Adam launch
     // below (DQNX_PER_FUSED=0: its own launch)
     PerUpdateArgs pua;
@@ -2572,12 +2669,13 @@ int enqueue_apply(dqnx_engine* e, int flags, hipStream_t s) {
         pua.slots = at<int32_t>(e, e->off[DQNX_BUF_BATCH_IDX]);
         pua.abs_td = at<float>(e, e->off[DQNX_BUF_PER_ABS_TD]);
         pua.skip = PER_SKIP_PROP;
-        int rc = launch_per_update(pua, s);
+        int rc = (parts & 1) ? launch_per_update(pua, s) : (int)DQNX_OK;
         if (rc) return rc;
-    } else if (c.algo == DQNX_ALGO_PER_DOUBLE) {
+    } else if (c.algo == DQNX_ALGO_PER_DOUBLE && (parts & 1)) {
         int rc = enqueue_per_update(e, at<int32_t>(e, e->off[DQNX_BUF_BATCH_IDX]), s);
         if (rc) return rc;
     }
+    if (!(parts & 2)) return DQNX_OK;
     AdamArgs aa;
     memset(&aa, 0, sizeof(aa));
     aa.nseg = 0;
@@ -2603,11 +2701,19 @@ int enqueue_apply(dqnx_engine* e, int flags, hipStream_t s) {
     aa.lrd = c.lr;
     aa.batch_global = e->Bg;
     aa.with_loss = 1;
+    if (gscale) {   // (mode 2 reads no loss partials: their slot carries the coefficient's address)
+        aa.gscale = gscale;
+        aa.clip = 1;
+    }
     if (keep_blk && dw_adam16_on(e, DQNX_STEP_GRADS_ONLY) && route_knob("DQNX_APPLY_TILES", 1) != 0) {
         // fused plan: k_dw_adam16 in apply mode -- 32 x 16 parameter tiles, the same per-element
         // update as k_adam, and each tile's blocked copies as (near-)contiguous blocks instead of
         // k_adam's per-element scattered stores (the DP shard step's last launch)
         DwAdam16Args da = apply_dw16_args(e, aa);
+        if (gscale) {
+            da.gscale = gscale;
+            da.clip = 1;
+        }
         if (prop_in_adam) {
             da.pprop = pua;
             da.pprop_wgs = (e->Bg + 511) / 512;
@@ -3088,7 +3194,7 @@ int dqnx_engine_reset(dqnx_engine* e, void* stream) {
     const int ids[] = {DQNX_BUF_GRADS, DQNX_BUF_ADAM_M, DQNX_BUF_ADAM_V, DQNX_BUF_CTRL, DQNX_BUF_RING_OBS,
                        DQNX_BUF_RING_NEXT_OBS, DQNX_BUF_RING_ACT, DQNX_BUF_RING_REW, DQNX_BUF_RING_DONE,
                        DQNX_BUF_SUMTREE, DQNX_BUF_BATCH_IDX, DQNX_BUF_Q, DQNX_BUF_TD, DQNX_BUF_IS_WEIGHTS,
-                       DQNX_BUF_WORKSPACE, DQNX_BUF_PER_ABS_TD, DQNX_BUF_LEARN_STATS};
+                       DQNX_BUF_WORKSPACE, DQNX_BUF_PER_ABS_TD, DQNX_BUF_LEARN_STATS, DQNX_BUF_GRAD_CLIP};
     for (int id : ids)
         if (e->bytes[id]) DQNX_HIP_CHECK(hipMemsetAsync(e->arena + e->off[id], 0, e->bytes[id], s));
     // SumTree.max/min_priority_index start at capacity - 1 (R:dqn/utils/sum_tree.py:12-13)
@@ -3498,7 +3604,9 @@ static int learn_step_side_fused(dqnx_engine* e, int base, bool prefetch, hipStr
     return DQNX_OK;
 }
 
-int dqnx_learn_step(dqnx_engine* e, int32_t flags, void* stream) {
+static int learn_step_clipped(dqnx_engine* e, int32_t flags, hipStream_t s);
+
+static int learn_step_impl(dqnx_engine* e, int32_t flags, void* stream) {
     int rc = check_bound(e);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
@@ -3566,6 +3674,70 @@ int dqnx_learn_step(dqnx_engine* e, int32_t flags, void* stream) {
     return DQNX_OK;
 }
 
+int dqnx_learn_step(dqnx_engine* e, int32_t flags, void* stream) {
+    int rc = check_bound(e);
+    if (rc) return rc;
+    // gradient clipping: a whole step is its gradient-only half, the clipping tail, the Adam half
+    if (clip_on(e) && !(flags & DQNX_STEP_GRADS_ONLY)) return learn_step_clipped(e, flags, (hipStream_t)stream);
+    return learn_step_impl(e, flags, stream);
+}
+
+// The second half of a step from DQNX_BUF_GRADS: dqnx_apply_grads (clip: with the clipping tail in
+// front and the coefficient in the Adam launch; stats_slot >= 0: a clipped learn step's statistics
+// launch behind it, reading the (idx, phys) pair of that slot).
+static int apply_impl(dqnx_engine* e, int32_t flags, bool clip, int stats_slot, hipStream_t stream) {
+    // with an in-launch prefetch pending the next step has no sampler launch: this pass writes the
+    // fused plan's blocked copies itself (measured 2.4-2.6 us per DP shard step faster than a
+    // relayout launch); otherwise the next sampler launch rebuilds them for free
+    // (the side-stream pipeline too: its next step has no sampler launch on the compute stream)
+    const bool keep = e->bwd_plan == 2 && e->pf_valid && (e->pf_inlaunch || route_knob("DQNX_SIDE_APPLY_KEEP", 1) != 0);
+    const int key = 0x100 | (flags & DQNX_STEP_SOFT_UPDATE) | (keep ? 0x200 : 0) | (keep && e->pf_inlaunch ? 0x400 : 0);
+    int rc2;
+    if (clip) {
+        const int tkey = KEY_CLIP_TAIL | (key & ~0x100) | (stats_slot >= 0 ? DQNX_STEP_STATS | (stats_slot << 8) : 0);
+        const std::vector<KStep>& ks = steps_for(e, tkey);
+        rc2 = run_graphed(e, 0x20000000 | tkey, stream, [&](hipStream_t s) { return enqueue_range(ks, 0, (int)ks.size(), s); });
+    } else {
+        rc2 = run_graphed(e, key, stream, [&](hipStream_t s) { return enqueue_apply(e, key, s); });
+    }
+    if (rc2) return rc2;
+    if (e->bwd_plan == 2 && e->pf_valid && !e->pf_inlaunch && e->side_stream) {   // (learn_step_side_fused: the captured join)
+        hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+        DQNX_HIP_CHECK(hipStreamIsCapturing(stream, &cst));
+        if (cst == hipStreamCaptureStatusActive) DQNX_HIP_CHECK(hipStreamWaitEvent(stream, e->ev_sampled[1], 0));
+    }
+    e->perm_dirty = true;   // (mode 2: the conv weights change without their permuted copies)
+    if (keep) e->wblk_dirty = false;                          // every blocked copy rewritten from the new weights
+    else if (!adam_keeps_blk(e)) e->wblk_dirty = true;        // this Adam pass leaves the blocked copies behind
+    return DQNX_OK;
+}
+
+// A learn step while clipping is on (include/dqnx.h "gradient clipping"): the DQNX_STEP_GRADS_ONLY step
+// with every form of drawing ahead it has, then the clipped apply; the same calls a data-parallel
+// caller makes, so every bookkeeping rule is theirs.
+static int learn_step_clipped(dqnx_engine* e, int32_t flags, hipStream_t s) {
+    int rc = stats_refused(e, flags);
+    if (rc) return rc;
+    const bool stats = (flags & DQNX_STEP_STATS) != 0;
+    int inner = (flags & (DQNX_STEP_GIVEN_INDICES | DQNX_STEP_PREFETCH)) | DQNX_STEP_GRADS_ONLY;
+    // (as the unclipped statistics step of the micro-CNN plan: nothing drawn ahead, the in-launch draw
+    // would overwrite the step's indices before the statistics launch reads them)
+    if (e->micro && stats) inner &= ~DQNX_STEP_PREFETCH;
+    // the (idx, phys) pair this step computes on: the per-layer side-stream pipeline alternates the slots
+    const int slot = (e->pf_valid && !e->pf_inlaunch && e->bwd_plan != 2) ? e->pf_slot : 0;
+    rc = learn_step_impl(e, inner, s);
+    if (rc) return rc;
+    rc = apply_impl(e, flags & DQNX_STEP_SOFT_UPDATE, true, stats ? slot : -1, s);
+    if (rc) return rc;
+    // The side-stream pipeline lets the draw after next overwrite this step's (idx, phys) pair once
+    // ev_computed[slot] has passed, and the gradient-only half recorded it before the tail.  The
+    // statistics launch at the tail's end still reads the pair (its ring rows): record the event again
+    // behind it -- the draw into this slot is enqueued by the NEXT step and waits on the latest record.
+    if (stats && e->bwd_plan != 2 && e->ev_computed[slot] && e->pf_computed_valid[slot])
+        DQNX_HIP_CHECK(hipEventRecord(e->ev_computed[slot], s));
+    return DQNX_OK;
+}
+
 // `count` consecutive learn steps as ONE graph (pure learning loops, e.g. several learn steps
 // per environment step): the first step's minibatch is drawn by the sampler launch, every
 // later one by the previous step's forward launch (in-launch prefetch), the last step draws
@@ -3582,7 +3754,7 @@ int dqnx_learn_steps(dqnx_engine* e, int32_t flags, int32_t count, void* stream)
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int base = flags & (DQNX_STEP_SOFT_UPDATE | DQNX_STEP_STATS);
-    if (e->pf_valid || !inlaunch_prefetch_ok(e, base)) {
+    if (e->pf_valid || !inlaunch_prefetch_ok(e, base) || clip_on(e)) {   // (clipped steps: one by one)
         for (int i = 0; i < count; i++) {
             rc = dqnx_learn_step(e, base, stream);
             if (rc) return rc;
@@ -3612,8 +3784,17 @@ int dqnx_learn_steps(dqnx_engine* e, int32_t flags, int32_t count, void* stream)
 // in-launch prefetch applies) the steady-state step of a prefetching loop -- no sampler launch,
 // the last launch draws the next minibatch (into slot 1; timing runs leave the state stale).
 static int timing_key(const dqnx_engine* e, int32_t flags) {
-    const int base = flags & (7 | DQNX_STEP_STATS);
-    if ((flags & DQNX_STEP_PREFETCH) && inlaunch_prefetch_ok(e, base)) return base | KEY_SAMPLE_NEXT;
+    int base = flags & (7 | DQNX_STEP_STATS);
+    const bool micro_stats = e->micro && (flags & DQNX_STEP_STATS);
+    const bool next = (flags & DQNX_STEP_PREFETCH) && inlaunch_prefetch_ok(e, base) && !micro_stats;
+    // (clipping on: the whole step's launches, the clipping tail included)
+    if (clip_on(e) && !(base & DQNX_STEP_GRADS_ONLY)) {
+        base |= KEY_CLIP;
+        // (its Adam pass leaves the fused plan's blocked copies behind unless it keeps them: the sampler
+        // launch of every such step rebuilds them)
+        if (!next && e->bwd_plan == 2 && !adam_keeps_blk(e)) base |= KEY_RELAYOUT;
+    }
+    if (next) return base | KEY_SAMPLE_NEXT;
     return base;
 }
 
@@ -3775,23 +3956,8 @@ int dqnx_apply_grads(dqnx_engine* e, int32_t flags, void* stream) {
     if (flags & DQNX_STEP_STATS)
         return set_error(DQNX_EUNSUPPORTED, "DQNX_STEP_STATS is out of scope for %s: the statistics launch ends a whole "
                                             "single-GPU learn step", "dqnx_apply_grads");
-    // with an in-launch prefetch pending the next step has no sampler launch: this pass writes the
-    // fused plan's blocked copies itself (measured 2.4-2.6 us per DP shard step faster than a
-    // relayout launch); otherwise the next sampler launch rebuilds them for free
-    // (the side-stream pipeline too: its next step has no sampler launch on the compute stream)
-    const bool keep = e->bwd_plan == 2 && e->pf_valid && (e->pf_inlaunch || route_knob("DQNX_SIDE_APPLY_KEEP", 1) != 0);
-    const int key = 0x100 | (flags & DQNX_STEP_SOFT_UPDATE) | (keep ? 0x200 : 0) | (keep && e->pf_inlaunch ? 0x400 : 0);
-    const int rc2 = run_graphed(e, key, (hipStream_t)stream, [&](hipStream_t s) { return enqueue_apply(e, key, s); });
-    if (rc2) return rc2;
-    if (e->bwd_plan == 2 && e->pf_valid && !e->pf_inlaunch && e->side_stream) {   // (learn_step_side_fused: the captured join)
-        hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
-        DQNX_HIP_CHECK(hipStreamIsCapturing((hipStream_t)stream, &cst));
-        if (cst == hipStreamCaptureStatusActive) DQNX_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, e->ev_sampled[1], 0));
-    }
-    e->perm_dirty = true;   // (mode 2: the conv weights change without their permuted copies)
-    if (keep) e->wblk_dirty = false;                          // every blocked copy rewritten from the new weights
-    else if (!adam_keeps_blk(e)) e->wblk_dirty = true;        // this Adam pass leaves the blocked copies behind
-    return DQNX_OK;
+    // (gradient clipping: the norm of what DQNX_BUF_GRADS holds now -- under DP the all-reduced gradient)
+    return apply_impl(e, flags, clip_on(e), -1, (hipStream_t)stream);
 }
 
 int dqnx_dp_bucket_count(dqnx_engine* e, int32_t* n) {
@@ -3889,6 +4055,9 @@ int dqnx_learn_step_bucket(dqnx_engine* e, int32_t flags, int32_t bucket, void* 
         return set_error(DQNX_EUNSUPPORTED, "DQNX_STEP_STATS is out of scope for %s: the statistics launch ends a whole "
                                             "single-GPU learn step", "dqnx_learn_step_bucket");
     if (flags & DQNX_STEP_GIVEN_INDICES) return set_error(DQNX_EUNSUPPORTED, "bucketed steps sample their own minibatch");
+    if (clip_on(e))
+        return set_error(DQNX_EUNSUPPORTED, "gradient clipping is on: %s is out of scope (a bucket's Adam runs before the "
+                                            "last bucket's gradient exists)", "dqnx_learn_step_bucket");
     std::vector<DpBucket> b;
     rc = dp_buckets(e, b);
     if (rc) return rc;
@@ -3927,6 +4096,9 @@ int dqnx_apply_grads_bucket(dqnx_engine* e, int32_t flags, int32_t bucket, void*
     if (flags & DQNX_STEP_STATS)
         return set_error(DQNX_EUNSUPPORTED, "DQNX_STEP_STATS is out of scope for %s: the statistics launch ends a whole "
                                             "single-GPU learn step", "dqnx_apply_grads_bucket");
+    if (clip_on(e))
+        return set_error(DQNX_EUNSUPPORTED, "gradient clipping is on: %s is out of scope (a bucket's Adam runs before the "
+                                            "last bucket's gradient exists)", "dqnx_apply_grads_bucket");
     hipStream_t s = (hipStream_t)stream;
     std::vector<DpBucket> b;
     rc = dp_buckets(e, b);
@@ -4906,6 +5078,7 @@ int dqnx_state_load(dqnx_engine* e, const void* src_host, uint64_t bytes, void* 
     if (e->ws_npc) DQNX_HIP_CHECK(hipMemsetAsync(e->arena + e->ws_npc, 0, 256, s));
     // the learn statistics are a log window's, not the run's: a restored run starts an empty one
     DQNX_HIP_CHECK(hipMemsetAsync(e->arena + e->off[DQNX_BUF_LEARN_STATS], 0, e->bytes[DQNX_BUF_LEARN_STATS], s));
+    DQNX_HIP_CHECK(hipMemsetAsync(e->arena + e->off[DQNX_BUF_GRAD_CLIP], 0, sizeof(dqnx_grad_clip_info), s));
     if (e->stride16 && n > 0) {   // a bf16 engine gathers the bf16 copies of the rows
         Ring16Args ra;
         memset(&ra, 0, sizeof(ra));
@@ -4955,6 +5128,38 @@ int dqnx_learn_stats_get(dqnx_engine* e, dqnx_learn_stats* out_host, int32_t res
                                   hipMemcpyDeviceToHost, s));
     DQNX_HIP_CHECK(hipStreamSynchronize(s));
     return reset ? dqnx_learn_stats_reset(e, stream) : (int)DQNX_OK;
+}
+
+int dqnx_set_grad_clip(dqnx_engine* e, double max_norm) {
+    if (!e) return set_error(DQNX_EINVAL, "engine is null");
+    if (max_norm != max_norm) return set_error(DQNX_EINVAL, "grad clip: max_norm is not a number");
+    int rc = state_pending(e, "set grad clip");
+    if (rc) return rc;
+    const double v = max_norm > 0.0 ? max_norm : 0.0;
+    if (v == e->grad_clip) return DQNX_OK;
+    e->grad_clip = v;
+    drop_graphs(e);   // max_norm is a launch argument of the cached plans
+    return DQNX_OK;
+}
+
+int dqnx_get_grad_clip(const dqnx_engine* e, double* max_norm) {
+    if (!e || !max_norm) return set_error(DQNX_EINVAL, "null argument");
+    *max_norm = e->grad_clip;
+    return DQNX_OK;
+}
+
+int dqnx_grad_clip_info_get(dqnx_engine* e, dqnx_grad_clip_info* out_host, int32_t reset, void* stream) {
+    int rc = check_bound(e);
+    if (rc) return rc;
+    if (!out_host) return set_error(DQNX_EINVAL, "null argument");
+    rc = state_pending(e, "grad clip info read");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    char* blk = e->arena + e->off[DQNX_BUF_GRAD_CLIP];
+    DQNX_HIP_CHECK(hipMemcpyAsync(out_host, blk, sizeof(dqnx_grad_clip_info), hipMemcpyDeviceToHost, s));
+    DQNX_HIP_CHECK(hipStreamSynchronize(s));
+    if (reset) DQNX_HIP_CHECK(hipMemsetAsync(blk, 0, sizeof(dqnx_grad_clip_info), s));
+    return DQNX_OK;
 }
 
 int dqnx_debug_stamps(dqnx_engine* e, int64_t* out64, void* stream) {

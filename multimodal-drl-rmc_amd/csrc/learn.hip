@@ -712,6 +712,10 @@ __device__ __forceinline__ bool adam_extra_wg(const AdamArgs& a) {
     return true;
 }
 
+// CLIP (mode 2 with AdamArgs::gscale, gradient clipping): every gradient element times the step's
+// coefficient first.  A template parameter, so that the kernels every other step launches are compiled
+// from exactly the code they had before clipping existed.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
     if (adam_extra_wg(a)) return;   // the sampler-cache / staged-minibatch workgroups
     const int eb = (int)blockIdx.x - adam_extra_count(a);   // element block
@@ -722,6 +726,8 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
         step_size = a.ctrl->adam_step_size;
         bc2s = a.ctrl->adam_bc2_sqrt;
     }
+    float gs = 1.f;
+    if constexpr (CLIP) gs = *a.gscale;   // the step's clip coefficient (k_clip_coef, an earlier launch)
     for (int64_t e = a.e0 + (int64_t)eb * blockDim.x + threadIdx.x; e < P; e += stride) {
         // every load of this element is issued before the first use (one round trip)
         float m = 0.f, v = 0.f, p = 0.f, tg = 0.f;
@@ -734,6 +740,7 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
         float gsum;
         if (a.mode == 2) {
             gsum = a.grads[e];
+            if constexpr (CLIP) gsum *= gs;   // g * coef, then the arithmetic below
         } else {
             // the element's segment by static-index selects (a kernel-argument array indexed by a
             // per-lane value would be copied to scratch)
@@ -880,6 +887,7 @@ __device__ __forceinline__ void adam_bounds_error(const AdamArgs& a, int site) {
     if (a.ctrl) __hip_atomic_store(&a.ctrl->error, (int32_t)site, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+template <bool CLIP>
 __global__ __launch_bounds__(256) void k_adam4(AdamArgs a) {
     if (adam_extra_wg(a)) return;   // the sampler-cache / staged-minibatch workgroups
     const int eb = (int)blockIdx.x - adam_extra_count(a);   // element block
@@ -903,6 +911,8 @@ __global__ __launch_bounds__(256) void k_adam4(AdamArgs a) {
         step_size = a.ctrl->adam_step_size;
         bc2s = a.ctrl->adam_bc2_sqrt;
     }
+    float gs = 1.f;
+    if constexpr (CLIP) gs = *a.gscale;   // the step's clip coefficient (mode 2 only: no wide path there)
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     const int64_t w0 = a.e0 >> 2, w4 = a.wide_end > a.e0 ? ((a.wide_end - a.e0) >> 2) : 0;
     const int wide_blocks = (int)((w4 * ADAM_WIDE + 255) / 256);
@@ -1030,6 +1040,9 @@ __global__ __launch_bounds__(256) void k_adam4(AdamArgs a) {
         }
         if (a.mode == 2) {
             g = ld(a.grads);
+            if constexpr (CLIP) {   // g * coef, then adam4_compute's arithmetic
+                g.x *= gs; g.y *= gs; g.z *= gs; g.w *= gs;
+            }
         } else {
             const AdamSegment sg = adam_segment_of(a, e);
             const float* pp = sg.partial + (e - sg.off) - e;   // ld() adds e back
@@ -1097,7 +1110,8 @@ __device__ __forceinline__ int64_t dw16_index(const DwAdam16Layer& d, int row, i
 }
 
 // R: 16-row blocks of W per workgroup (a tile is 16 R x 16; every X element loaded feeds R MFMAs)
-template <int DW16_NW, int U, int R>   // waves per tile; k-steps (4 rows each) per register set, two sets in flight
+// CLIP: the apply mode (3) with DwAdam16Args::gscale, gradient clipping (as k_adam's)
+template <int DW16_NW, int U, int R, bool CLIP = false>   // waves per tile; k-steps (4 rows each) per register set, two sets in flight
 __global__ __launch_bounds__(64 * DW16_NW) void k_dw_adam16(DwAdam16Args a) {
     __shared__ floatx4 red[DW16_NW][R][64];
     __shared__ float redb[DW16_NW][R][64];
@@ -1174,6 +1188,8 @@ __global__ __launch_bounds__(64 * DW16_NW) void k_dw_adam16(DwAdam16Args a) {
         }
     }
     const float step_size = gld(&a.ctrl->adam_step_size), bc2s = gld(&a.ctrl->adam_bc2_sqrt);
+    float gs = 1.f;
+    if constexpr (CLIP) gs = gld(a.gscale);   // the step's clip coefficient (k_clip_coef, an earlier launch)
     DQNX_STAMP(a.stamps, 57);
 
     // (1) dW tile = dZ[:, o0:o0+16]^T X[:, i0:i0+16] over this wave's rows; lane (i, g) supplies
@@ -1256,6 +1272,7 @@ __global__ __launch_bounds__(64 * DW16_NW) void k_dw_adam16(DwAdam16Args a) {
         float gsum;
         if (apply) {
             gsum = ga[j];
+            if constexpr (CLIP) gsum *= gs;
         } else if (q < NW_) {   // row block r = q / 256 of the tile; the same order for every R
             const float* rf = reinterpret_cast<const float*>(&red[0][0][0]) + (q >> 8) * 256;
             const int qq = q & 255, rr = qq >> 4, off = ((rr >> 2) * 16 + (qq & 15)) * 4 + (rr & 3);
@@ -1312,6 +1329,12 @@ int launch_dw_adam16(const DwAdam16Args& a, hipStream_t s) {
     if (a.ptrack && (a.pprop.n > PER_CHUNK || !a.pprop.sync || a.pprop_wgs < 1))
         return set_error(DQNX_EINVAL, "dw_adam16: PER tracking workgroup needs its prop workgroups and hand-off words");
     const dim3 grid(a.tiles + a.ptrack + (a.mtc ? 1 : 0) + (a.pf_nidx > 0 ? 1 : 0) + a.pprop_wgs);
+    if (a.clip) {   // a clipped dqnx_apply_grads: the default 32 x 16 tiles (apply_dw16_args)
+        if (a.mode != 3 || a.rows16 != 2 || !a.gscale) return set_error(DQNX_EINVAL, "dw_adam16: a clip coefficient outside the apply mode");
+        DQNX_LAUNCH((k_dw_adam16<8, 8, 2, true>), grid, dim3(512), 0, s, a);
+        DQNX_HIP_CHECK(hipGetLastError());
+        return DQNX_OK;
+    }
     if (a.rows16 == 2) {
         switch (var) {   // measurement variants (waves per tile, k-steps per register set)
             case 7: DQNX_LAUNCH((k_dw_adam16<16, 4, 2>), grid, dim3(1024), 0, s, a); break;
@@ -1626,8 +1649,15 @@ int launch_adam(const AdamArgs& a_in, hipStream_t s) {
     if (a.mtc) blocks++;   // + the sampler-cache workgroup
     if (a.pf_nidx > 0) blocks++;   // + the staged-minibatch copy
     blocks += a.pprop_wgs;         // + k_per_prop's workgroups (256 updates each)
-    if (vec) DQNX_LAUNCH(k_adam4, dim3(blocks), dim3(256), 0, s, a);
-    else DQNX_LAUNCH(k_adam, dim3(blocks), dim3(256), 0, s, a);
+    if (a.clip) {   // a clipped dqnx_apply_grads
+        if (a.mode != 2 || !a.gscale) return set_error(DQNX_EINVAL, "adam: a clip coefficient outside the grads -> Adam mode");
+        if (vec) DQNX_LAUNCH(k_adam4<true>, dim3(blocks), dim3(256), 0, s, a);
+        else DQNX_LAUNCH(k_adam<true>, dim3(blocks), dim3(256), 0, s, a);
+    } else if (vec) {
+        DQNX_LAUNCH(k_adam4<false>, dim3(blocks), dim3(256), 0, s, a);
+    } else {
+        DQNX_LAUNCH(k_adam<false>, dim3(blocks), dim3(256), 0, s, a);
+    }
     DQNX_HIP_CHECK(hipGetLastError());
     return DQNX_OK;
 }

@@ -203,11 +203,17 @@ struct AdamArgs {
     float* target;
     dqnx_ctrl* ctrl;
     float w1, beta2, c2, eps, tau, one_minus_tau;
-    const float* loss_partial;
+    // (gradient clipping adds no bytes to the kernel arguments: the coefficient's address shares the slot
+    // of the loss partials, which mode 2 never reads, and the flag sits in what was padding)
+    union {
+        const float* loss_partial;   // modes 0 / 1: the loss tiles' partials
+        const float* gscale;         // mode 2 with `clip`: every gradient element times *gscale first
+    };
     int n_loss_partial;
     int batch_global;
     const float* adam_table;   // [t-1] = {-lr/bc1, bc2**0.5} for t <= adam_table_len (host libm)
     int adam_table_len;
+    int clip;                  // mode 2: multiply the gradient by *gscale (launch_adam picks the kernel by it)
     double beta1d, beta2d, lrd;
     uint32_t* mtc;         // uniform sampler's MT block cache, extended by an extra workgroup (or null)
     int mtc_blocks;
@@ -365,11 +371,15 @@ struct DwAdam16Args {
     float* target;
     dqnx_ctrl* ctrl;
     float w1, beta2, c2, eps, tau, one_minus_tau;
-    const float* loss_partial;
+    union {   // (one slot and a flag in former padding, as AdamArgs')
+        const float* loss_partial;   // modes 0 / 1
+        const float* gscale;         // mode 3 with `clip`: every gradient element times *gscale first
+    };
     int n_loss_partial;
     int batch_global;
     uint32_t* mtc;
     int mtc_blocks;
+    int clip;              // mode 3: multiply the gradient by *gscale (launch_dw_adam16 picks the kernel by it)
     int64_t* stamps;       // diagnostic builds (-DDQNX_STAMPS): slots 56..61
     // in-launch prefetch (DQNX_STEP_PREFETCH): one more workgroup copies the minibatch the forward
     // launch drew into the staging slot over this step's (pf_nidx = 0: none)
@@ -875,6 +885,28 @@ struct StatsArgs {
 };
 uint64_t stats_part_bytes(int n_bwg, int n_chunks);
 int launch_learn_stats(const StatsArgs& a, hipStream_t s);
+
+// Gradient clipping (clip.hip; include/dqnx.h "gradient clipping"): two launches between the gradient
+// and the Adam pass that reads it.  k_grad_sumsq: workgroup b sums g^2 over elements [b chunk, (b + 1)
+// chunk) of the flat gradient into part[b]; k_clip_coef: one workgroup folds the partials in index
+// order, writes the step's coefficient to *coef and updates the info block.
+constexpr int kClipThreads = 256;
+constexpr int kClipMinChunk = 4096;    // elements per workgroup (a multiple of 4), doubled ...
+constexpr int kClipMaxParts = 512;     // ... until at most this many workgroups
+constexpr uint64_t kClipCoefOff = 64, kClipPartOff = 128;   // byte offsets inside DQNX_BUF_GRAD_CLIP
+struct ClipArgs {
+    const float* grads;          // [n_params] (16-byte aligned); the loss slot behind it is not read
+    int64_t n_params;
+    int64_t chunk;               // elements per workgroup, a multiple of 4
+    int n_part;                  // workgroups = partials: ceil(n_params / chunk)
+    double* part;                // [n_part]
+    float* coef;                 // the coefficient the Adam pass multiplies by
+    dqnx_grad_clip_info* info;
+    float max_norm;
+};
+void clip_geometry(int64_t n_params, int64_t* chunk, int* n_part);
+int launch_grad_sumsq(const ClipArgs& a, hipStream_t s);
+int launch_clip_coef(const ClipArgs& a, hipStream_t s);
 
 int launch_sample_uniform(const SampleArgs& a, hipStream_t s);
 int launch_idx_to_phys(const int32_t* idx, int32_t* phys, int shard_begin, int n, dqnx_ctrl* ctrl, int64_t capacity,

@@ -25,7 +25,7 @@ DQNX_ALGO_DQN, DQNX_ALGO_DOUBLE, DQNX_ALGO_PER_DOUBLE = 0, 1, 2
 DQNX_MAX_DENSE, DQNX_MAX_CONV = 6, 4
 (BUF_PARAMS, BUF_TARGET_PARAMS, BUF_GRADS, BUF_ADAM_M, BUF_ADAM_V, BUF_CTRL, BUF_RING_OBS,
  BUF_RING_NEXT_OBS, BUF_RING_ACT, BUF_RING_REW, BUF_RING_DONE, BUF_SUMTREE, BUF_BATCH_IDX, BUF_Q,
- BUF_TD, BUF_IS_WEIGHTS, BUF_WORKSPACE, BUF_PER_ABS_TD, BUF_LEARN_STATS, BUF_COUNT) = range(20)
+ BUF_TD, BUF_IS_WEIGHTS, BUF_WORKSPACE, BUF_PER_ABS_TD, BUF_LEARN_STATS, BUF_GRAD_CLIP, BUF_COUNT) = range(21)
 DQNX_RNG_PY, DQNX_RNG_NP = 0, 1
 STEP_SOFT_UPDATE = 0x1
 STEP_GIVEN_INDICES = 0x2
@@ -104,6 +104,12 @@ class LearnStats(ctypes.Structure):
     ]
 
 
+# gradient clipping (dqnx.h "gradient clipping")
+class GradClipInfo(ctypes.Structure):
+    _fields_ = [("steps", I64), ("clipped_steps", I64), ("norm_sum", ctypes.c_double), ("norm_max", ctypes.c_double),
+                ("last_norm", ctypes.c_float), ("last_coef", ctypes.c_float)]
+
+
 # training-state snapshot (dqnx.h "training-state snapshot")
 STATE_MAGIC = 0x54415453584E5144   # b"DQNXSTAT" little-endian
 STATE_VERSION = 1
@@ -146,6 +152,7 @@ EXPORTS = [
     "dqnx_act_host", "dqnx_agent_learn_mt", "dqnx_agent_quiesce", "dqnx_agent_choose", "dqnx_act_kernel_count",
     "dqnx_state_bytes", "dqnx_state_save", "dqnx_state_load", "dqnx_state_inspect",
     "dqnx_learn_stats_get", "dqnx_learn_stats_reset",
+    "dqnx_set_grad_clip", "dqnx_get_grad_clip", "dqnx_grad_clip_info_get",
 ]
 
 GIL_HELD = ("dqnx_agent_learn_mt", "dqnx_agent_choose")   # entry points called with the GIL held (see lib())
@@ -233,6 +240,9 @@ def lib():
         "dqnx_state_inspect": ([vp, ctypes.c_uint64, P(StateInfo)], ctypes.c_int),
         "dqnx_learn_stats_get": ([vp, P(LearnStats), I32, vp], ctypes.c_int),
         "dqnx_learn_stats_reset": ([vp, vp], ctypes.c_int),
+        "dqnx_set_grad_clip": ([vp, ctypes.c_double], ctypes.c_int),
+        "dqnx_get_grad_clip": ([vp, P(ctypes.c_double)], ctypes.c_int),
+        "dqnx_grad_clip_info_get": ([vp, P(GradClipInfo), I32, vp], ctypes.c_int),
     }
     # dqnx_agent_learn_mt reads and writes random._inst's MT words in place: call it through a PyDLL
     # handle, which keeps the GIL for the call (a CDLL call releases it, and another thread's `random`

@@ -76,6 +76,14 @@ def _learn_stats_on() -> bool:
     return os.environ.get("DQNX_LEARN_STATS", "0") not in ("", "0")
 
 
+def _grad_clip_env():
+    """DQNX_GRAD_CLIP=<max_norm>: clip the global norm of every learn step's gradient before Adam
+    (torch.nn.utils.clip_grad_norm_ between backward() and step()), so an unmodified train.py gets it.
+    Unset, empty or <= 0 (default): the reference's behaviour, no clipping."""
+    v = os.environ.get("DQNX_GRAD_CLIP", "")
+    return float(v) if v.strip() else None
+
+
 def _summary_writer(log_dir):
     try:
         from torch.utils.tensorboard import SummaryWriter
@@ -235,7 +243,7 @@ class Agent:
                                   lr=self.lr, tau=self.target_soft_update_tau, n_env=self.n_env, device=self.device,
                                   eps_dec=self.epsilon_decay,
                                   compute_dtype=os.environ.get("DQNX_COMPUTE_DTYPE", "fp32"),
-                                  per_numpy121=_per_numpy121())
+                                  per_numpy121=_per_numpy121(), grad_clip=_grad_clip_env())
         self.online_network.bind_flat(self.engine.param_views(self.engine.params), self.engine.params, spec,
                                       engine=self.engine)
         self.target_network.bind_flat(self.engine.param_views(self.engine.target_params), self.engine.target_params,
@@ -559,6 +567,21 @@ class Agent:
         self._launch_pending()   # a recorded step keeps the setting it was recorded under
         self.engine.collect_stats = bool(on)
 
+    def set_grad_clip(self, max_norm) -> None:
+        """Clip the global norm of every following learn step's gradient to max_norm before Adam, on the
+        device (None or <= 0: off, the default; DQNX_GRAD_CLIP=<max_norm> sets it at construction).
+        While it is on, log() writes GradNorm (the window's mean pre-clip norm) and GradClipFrac."""
+        self.engine.set_grad_clip(max_norm)   # (launches a recorded step and consumes its readback first)
+
+    def _log_grad_clip(self, step):
+        """The log window's clipping scalars (one blocking read, then the block is zeroed)."""
+        ci = self.engine.grad_clip_info(reset=True)
+        if ci["steps"] == 0:
+            return
+        if not self.engine.collect_stats:   # (the training statistics write the same window mean)
+            self.summary_writer.add_scalar('GradNorm', ci["norm_mean"], global_step=step)
+        self.summary_writer.add_scalar('GradClipFrac', ci["clipped_frac"], global_step=step)
+
     def _log_learn_stats(self, step):
         """The scalars of the log window's training statistics (one blocking read, then the block is
         zeroed for the next window); returns the window's mean loss, or None for an empty window."""
@@ -596,6 +619,8 @@ class Agent:
             self.summary_writer.add_scalar('AvgEpLen', len_mean, global_step=self.step * self.n_env)
             self.summary_writer.add_scalar('Episodes', self.episode_count, global_step=self.step * self.n_env)
             loss = self._log_learn_stats(self.step * self.n_env) if self.engine.collect_stats else None
+            if self.engine.grad_clip > 0:
+                self._log_grad_clip(self.step * self.n_env)
             self.summary_writer.add_scalar('Loss', self.engine.loss() if loss is None else loss,
                                            global_step=self.step * self.n_env)
             self.summary_writer.add_scalar('LearnTransitionsPerSec', self.learn_throughput(),

@@ -210,8 +210,10 @@ class LearnEngine:
 
     def __init__(self, spec: NetSpec, algo: str, batch: int, capacity: int, gamma=0.99, lr=1e-4,
                  tau=1e-3, n_env=1, world_size=1, rank=0, device=None, graphs=False, eps_dec=2e6,
-                 local_sampling=False, compute_dtype="fp32", per_numpy121=False):
-        """graphs: replay each learn step as a captured HIP graph (off by default: eager launches
+                 local_sampling=False, compute_dtype="fp32", per_numpy121=False, grad_clip=None):
+        """grad_clip: max_norm of torch.nn.utils.clip_grad_norm_ applied to every step's gradient before
+        Adam, on the device (None or <= 0: off; set_grad_clip changes it later).
+        graphs: replay each learn step as a captured HIP graph (off by default: eager launches
         measured 3-4 us faster per step, include/dqnx.h dqnx_engine_set_graphs).
         per_numpy121: PER SumTree arithmetic of the reference's pinned numpy 1.21 (float32
         `change` and float32-rounded ancestor sums, in update order) instead of numpy >= 2's."""
@@ -272,6 +274,7 @@ class LearnEngine:
         self.learn_stats_view = self.view(C.BUF_LEARN_STATS, torch.uint8)   # one dqnx_learn_stats (C.LearnStats)
         # agent_launch / agent_learn_mt steps also accumulate the training statistics (DQNX_STEP_STATS)
         self.collect_stats = False
+        self.grad_clip = 0.0
         self.ring_size = 0
         self.ring_wptr = 0
         self.agent_step = 0      # host mirror of dqnx_ctrl.agent_step (PER beta schedule)
@@ -280,6 +283,8 @@ class LearnEngine:
         # `settle_hook` also waits for it and raises a device error it reported
         self.launch_hook = None
         self.settle_hook = None
+        if grad_clip is not None:
+            self.set_grad_clip(grad_clip)
 
     def launch_recorded(self):
         if self.launch_hook is not None:
@@ -628,6 +633,33 @@ class LearnEngine:
         names = [name for name, _, _ in self.param_layout]
         d["grad_norm_last"] = {n: float(np.sqrt(g)) for n, g in zip(names, d["grad_sq_last"])}
         d["param_norm_last"] = {n: float(np.sqrt(p)) for n, p in zip(names, d["param_sq_last"])}
+        return d
+
+    # ---- gradient clipping (dqnx_*_grad_clip*: include/dqnx.h "gradient clipping") -------------------
+    def set_grad_clip(self, max_norm) -> None:
+        """Clip the global L2 norm of every following step's gradient to max_norm before Adam, as
+        torch.nn.utils.clip_grad_norm_(params, max_norm) would between backward() and step(); None
+        or <= 0 turns it off.  Configuration like lr: not part of the training-state blob."""
+        self.settle()   # a drop-in Agent's recorded step runs under the setting it was recorded with
+        v = 0.0 if max_norm is None else float(max_norm)
+        C.check(self.L.dqnx_set_grad_clip(self.h, ctypes.c_double(v)), "set_grad_clip")
+        out = ctypes.c_double()
+        C.check(self.L.dqnx_get_grad_clip(self.h, ctypes.byref(out)), "get_grad_clip")
+        self.grad_clip = float(out.value)
+
+    def grad_clip_info(self, reset=False) -> dict:
+        """What the clipped steps since the last reset saw: ONE blocking read, meant for log cadence.
+        steps, clipped_steps (coef < 1), norm_sum / norm_max / last_norm (the PRE-clip global norm),
+        last_coef, and the window's norm_mean and clipped_frac (0 for an empty window)."""
+        self.settle()
+        st = C.GradClipInfo()
+        C.check(self.L.dqnx_grad_clip_info_get(self.h, ctypes.byref(st), 1 if reset else 0, self.stream()),
+                "grad_clip_info_get")
+        d = {"steps": int(st.steps), "clipped_steps": int(st.clipped_steps), "norm_sum": float(st.norm_sum),
+             "norm_max": float(st.norm_max), "last_norm": float(st.last_norm), "last_coef": float(st.last_coef)}
+        steps = max(d["steps"], 1)
+        d["norm_mean"] = d["norm_sum"] / steps
+        d["clipped_frac"] = d["clipped_steps"] / steps
         return d
 
     # ---- training-state snapshot (dqnx_state_*: include/dqnx.h "training-state snapshot") ----------
