@@ -2039,6 +2039,9 @@ static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
 #endif
             k.run = [=](hipStream_t s) { return launch_linear_fwd_split(fa, np_, act, vecb, s); };
             ks.push_back(k);
+            // one slab (F < 256, or more tiles than compute units): the kernel's epilogue already wrote
+            // act(sum + bias) into H; a reduce would overwrite it from the slabs it never filled
+            if (fa.ksplit == 1) continue;
             KStep kr;
             kr.name = k.name + "_reduce";
             kr.bytes = 4.0 * ((double)fa.ksplit + 1) * np_ * Bl * lp.out;
@@ -2054,6 +2057,7 @@ static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
             fa.partial = at<float>(e, e->ws_part[l]);
             k.run = [=](hipStream_t s) { return launch_linear_fwd_big(fa, np_, act, vecb, s); };
             ks.push_back(k);
+            if (ksplit == 1) continue;   // (as above: the one-slab epilogue wrote H)
             KStep kr;
             kr.name = k.name + "_reduce";
             kr.bytes = 4.0 * ((double)ksplit + 1) * np_ * Bl * lp.out;

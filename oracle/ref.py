@@ -142,10 +142,15 @@ def mlp_spec(obs_dim=284, n_actions=8, head="dueling", hidden=(256, 128)) -> Net
     return NetSpec(kind="mlp", obs_dim=obs_dim, n_actions=n_actions, head=head, hidden=tuple(hidden))
 
 
-def hybrid_spec(n_actions=8, head="dueling", micro_chw=(2, 27, 5), macro_len=14) -> NetSpec:
+def hybrid_spec(n_actions=8, head="dueling", micro_chw=(2, 27, 5), macro_len=14, conv=None, dense=None) -> NetSpec:
     c, h, w = micro_chw
-    return NetSpec(kind="hybrid", obs_dim=macro_len + c * h * w, n_actions=n_actions, head=head,
+    spec = NetSpec(kind="hybrid", obs_dim=macro_len + c * h * w, n_actions=n_actions, head=head,
                    macro_len=macro_len, micro_chw=tuple(micro_chw))
+    if conv is not None:     # cnn_params / dense_params of network_config (R:env/dqn_config.py:148-193)
+        spec.conv = tuple((int(f), tuple(k), tuple(s)) for f, k, s in conv)
+    if dense is not None:
+        spec.dense = tuple(dense)
+    return spec
 
 
 def conv_out_hw(spec: NetSpec):

@@ -20,15 +20,21 @@ def _E():
     return E
 
 
-def make_hybrid_pair(algo, batch, cap, n_fill, seed, graphs=False, micro_chw=(2, 27, 5)):
+def make_hybrid_pair(algo, batch, cap, n_fill, seed, graphs=False, micro_chw=(2, 27, 5), geom=None):
+    """An oracle learner and an engine in the same state.  geom: a row of tests/conv_geoms.py (its
+    micro grid, macro length, conv stack and dense widths) in place of the reference's net on micro_chw."""
     E = _E()
     head = O.algo_spec_head(algo)
-    ospec = O.hybrid_spec(8, head, micro_chw=micro_chw)
+    if geom is None:
+        ospec, espec = O.hybrid_spec(8, head, micro_chw=micro_chw), E.hybrid_spec(8, head, micro_chw=micro_chw)
+    else:
+        import conv_geoms as G
+        ospec, espec = G.oracle_spec(O, geom, head), G.engine_spec(E, geom, head)
     init = O.reference_init(ospec, seed)
     oracle = O.OracleLearner(ospec, algo, batch, cap, seed=seed, params=init, per_pow="cr")
-    data = O.synth_transitions(n_fill, ospec.obs_dim, 8, seed=seed + 100)
+    data = O.synth_transitions(n_fill, ospec.obs_dim, 8, seed=seed + 100, macro_len=ospec.macro_len)
     O.fill_replay(oracle, *data)
-    eng = E.LearnEngine(E.hybrid_spec(8, head, micro_chw=micro_chw), algo, batch, cap, graphs=graphs)
+    eng = E.LearnEngine(espec, algo, batch, cap, graphs=graphs)
     eng.load_params(init)
     eng.push(*data)
     random.seed(seed + 7)
