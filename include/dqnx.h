@@ -356,7 +356,23 @@ int dqnx_hard_update(dqnx_engine* e, void* stream);
  * where that is the faster call (two or more convs whose first layers fit a workgroup's LDS, and
  * n <= 2 by default: DQNX_ACT_TS=2 takes it up to n = 256, DQNX_ACT_TS=0 never), else one launch
  * per conv layer; then the dense stream + head as for an MLP on cat(flatten(conv), macro).
- * dqnx_act_kernel_count reports the launches.  Stream-ordered, no sync. */
+ * dqnx_act_kernel_count reports the launches.  Stream-ordered, no sync.
+ *
+ * Nets that do not fit a workgroup's LDS -- a conv input image over 64 KB (the (4,84,84) variant), or
+ * a first dense layer of more than 8192 inputs -- are refused (DQNX_EUNSUPPORTED) unless the
+ * environment holds DQNX_ACT_LARGE, read whenever a net is planned (every entry point below, so set it
+ * before the first acting call of an object that decides its path once):
+ *   unset / 0  refused, as above;
+ *   1          such a net takes the LARGE route; nets that fit keep their kernels and launch counts;
+ *   2          every MLP and two-stream net takes the large route (for testing it at small shapes).
+ * The large route works through the n rows in chunks of at most 8, each chunk one banded launch per
+ * conv layer, dense 1 as a split-K weight stream, its reduce, and one launch for the rest of the net
+ * (layers 2..L + head as for an MLP on dense 1's output; the head alone for a one-layer body):
+ * dqnx_act_kernel_count = ceil(n / 8) * (convs + 3).  The chunks reuse the scratch in stream order, so
+ * dqnx_act_scratch_bytes(net, n) is one chunk's intermediates (min(n, 8) rows) plus the MLP kernels'
+ * part, and does not grow past n = 8; the scratch contract above holds unchanged.  dqnx_act_host and
+ * dqnx_agent_choose on this route always stage the obs, copy the actions back and synchronise the
+ * stream (no in-place pinned path, no completion word). */
 uint64_t dqnx_act_scratch_bytes(const dqnx_net_desc* net, int32_t n);
 int dqnx_act(const dqnx_net_desc* net, const float* params, const float* obs, int32_t n, int32_t* actions,
              float* values, void* scratch, uint64_t scratch_bytes, void* stream);

@@ -4165,15 +4165,24 @@ int dqnx_hard_update(dqnx_engine* e, void* stream) {
 // acting kernel geometry of a network (host only).  A two-stream net acts as its convs (one launch
 // for the whole stack where act_ts_plan applies, else one each; act_hybrid.hip) followed by the MLP
 // acting kernel on F = cat(flatten(conv), macro).
-static int act_plan_build(const dqnx_net_desc* net, NetPlan& np, ActArgs& a);
+static int act_plan_build(const dqnx_net_desc* net, NetPlan& np, ActArgs& a, int large_mode);
+
+// DQNX_ACT_LARGE, read at plan time: 0 (default) nets that do not fit LDS are refused; 1 they take the
+// large route (act_large.hip) and nets that fit keep their kernels; 2 every net takes the large route
+static int act_large_mode() {
+    const int m = route_knob("DQNX_ACT_LARGE", 0);
+    return m == 1 || m == 2 ? m : 0;
+}
 
 // act_plan for the acting path's every call (choose_actions: one per env step): the plans of the last
-// few network descriptions this thread acted with, keyed by the description's bytes (planning a net --
-// param layout, names -- costs ~3.4 us of host time, and dqnx_act_host / dqnx_agent_choose need it
-// three times per call).  *npp points into the cache: valid until this thread plans 4 other nets.
+// few network descriptions this thread acted with, keyed by the description's bytes and the value of
+// DQNX_ACT_LARGE they were planned under (planning a net -- param layout, names -- costs ~3.4 us of host
+// time, and dqnx_act_host / dqnx_agent_choose need it three times per call).  *npp points into the cache:
+// valid until this thread plans 4 other nets.
 static int act_plan(const dqnx_net_desc* net, const NetPlan** npp, ActArgs& a) {
     struct Entry {
         bool used = false;
+        int mode = 0;
         dqnx_net_desc desc;
         NetPlan np;
         ActArgs a;
@@ -4182,11 +4191,12 @@ static int act_plan(const dqnx_net_desc* net, const NetPlan** npp, ActArgs& a) {
     static thread_local Entry cache[4];
     static thread_local int next = 0;
     if (!net) return set_error(DQNX_EINVAL, "null net");
+    const int mode = act_large_mode();
     for (Entry& en : cache) {
-        if (en.used && !memcmp(&en.desc, net, sizeof(dqnx_net_desc))) {
+        if (en.used && en.mode == mode && !memcmp(&en.desc, net, sizeof(dqnx_net_desc))) {
             if (en.rc) {   // (re-raise its error message)
                 NetPlan tmp;
-                return act_plan_build(net, tmp, a);
+                return act_plan_build(net, tmp, a, mode);
             }
             *npp = &en.np;
             a = en.a;
@@ -4196,16 +4206,62 @@ static int act_plan(const dqnx_net_desc* net, const NetPlan** npp, ActArgs& a) {
     Entry& en = cache[next];
     next = (next + 1) & 3;
     en.used = true;
+    en.mode = mode;
     memcpy(&en.desc, net, sizeof(dqnx_net_desc));
     en.np = NetPlan();
-    en.rc = act_plan_build(net, en.np, en.a);
+    en.rc = act_plan_build(net, en.np, en.a, mode);
     if (en.rc) return en.rc;
     *npp = &en.np;
     a = en.a;
     return DQNX_OK;
 }
 
-static int act_plan_build(const dqnx_net_desc* net, NetPlan& np, ActArgs& a) {
+static void act_conv_args(const ConvPlan& cp, ActConvArgs& ca) {
+    memset(&ca, 0, sizeof(ca));
+    ca.Ci = cp.Ci; ca.Hi = cp.Hi; ca.Wi = cp.Wi; ca.Co = cp.Co; ca.Ho = cp.Ho; ca.Wo = cp.Wo;
+    ca.kh = cp.kh; ca.kw = cp.kw; ca.sh = cp.sh; ca.sw = cp.sw; ca.ph = cp.ph; ca.pw = cp.pw;
+}
+
+// The large route (act_large.hip) of a planned net, for calls of n rows.  Rows go through in chunks of at
+// most kActWideRows, each chunk reusing the scratch in stream order:
+//   [conv outputs of every conv but the last, Rc rows][F = dense input, Rc rows (two-stream nets)]
+//   [dense 1's split-K shares S x Rc x J][h1 Rc x J] -- `bytes` so far, a multiple of 256 --
+//   then the MLP acting kernel's part for layers 2..L on Rc rows (its tickets at the END of the buffer)
+// with Rc = min(n, kActWideRows).  `tail`: the net's layer tables shifted by one (input h1, D = out[0]).
+struct ActLargeLayout {
+    int Rc, S, Ls;
+    uint64_t F_off, part_off, h_off, bytes, mlp;
+    ActArgs tail;
+};
+static void act_large_layout(const dqnx_net_desc* net, const NetPlan& np, const ActArgs& a, int n, ActLargeLayout& y) {
+    const auto up = [](uint64_t b, uint64_t q) { return (b + q - 1) / q * q; };
+    y.Rc = std::max(0, std::min(n, kActWideRows));
+    act_wide_slices(a.D, &y.S, &y.Ls);
+    const uint64_t Rc = (uint64_t)y.Rc, J = (uint64_t)a.out[0];
+    uint64_t b = 0;
+    for (size_t l = 0; l + 1 < np.conv.size(); l++) b += Rc * np.conv[l].Co * np.conv[l].Ho * np.conv[l].Wo * 4;
+    y.F_off = b = up(b, 16);
+    if (net->kind != DQNX_NET_MLP) b += Rc * a.D * 4;
+    y.part_off = b = up(b, 16);
+    b += (uint64_t)y.S * Rc * J * 4;
+    y.h_off = b = up(b, 16);
+    b += Rc * J * 4;
+    y.bytes = up(b, 256);
+    ActArgs& t = y.tail;
+    t = a;
+    t.large = 0;
+    t.L = a.L - 1;
+    t.D = a.out[0];
+    t.ld = std::max(t.D, t.A);
+    for (int l = 0; l < t.L; l++) {
+        t.in[l] = a.in[l + 1]; t.out[l] = a.out[l + 1]; t.off[l] = a.off[l + 1];
+        t.ld = std::max(t.ld, t.out[l]);
+    }
+    t.ld = (t.ld + 3) & ~3;
+    y.mlp = t.L >= 1 ? act_scratch_bytes(y.Rc, t.out[0], t.ld, t.L, t.L >= 2 ? t.out[1] : 0) : 0;
+}
+
+static int act_plan_build(const dqnx_net_desc* net, NetPlan& np, ActArgs& a, int large_mode) {
     int rc = plan_net(net, np);
     if (rc) return rc;
     memset(&a, 0, sizeof(a));
@@ -4220,13 +4276,33 @@ static int act_plan_build(const dqnx_net_desc* net, NetPlan& np, ActArgs& a) {
     }
     a.ld = (a.ld + 3) & ~3;   // float4 LDS rows
     a.head_off = np.head_off;
+    // the large route: forced (2), or taken by a net the LDS-resident kernels refuse for its size (1)
+    bool large = large_mode == 2 && a.L >= 1;
+    if (large_mode == 1 && a.L >= 1 && act_rows_per_block(1, a.ld) == 0) large = true;
     for (const ConvPlan& cp : np.conv) {   // each conv's row image + one channel's weights in LDS
         ActConvArgs ca;
-        memset(&ca, 0, sizeof(ca));
-        ca.Ci = cp.Ci; ca.Hi = cp.Hi; ca.Wi = cp.Wi; ca.Ho = cp.Ho; ca.Wo = cp.Wo; ca.kh = cp.kh; ca.kw = cp.kw;
-        if (act_conv_lds_bytes(ca) > 64 * 1024)
-            return set_error(DQNX_EUNSUPPORTED, "dqnx_act: conv input %dx%dx%d too large for the acting kernel",
-                             cp.Ci, cp.Hi, cp.Wi);
+        act_conv_args(cp, ca);
+        if (act_conv_lds_bytes(ca) > 64 * 1024) {
+            if (large_mode == 0)
+                return set_error(DQNX_EUNSUPPORTED, "dqnx_act: conv input %dx%dx%d too large for the acting kernel",
+                                 cp.Ci, cp.Hi, cp.Wi);
+            large = true;
+        }
+    }
+    if (large) {
+        ActBandPlan bp;
+        for (const ConvPlan& cp : np.conv) {
+            ActConvArgs ca;
+            act_conv_args(cp, ca);
+            if (!act_band_plan(ca, bp))
+                return set_error(DQNX_EUNSUPPORTED, "dqnx_act: conv window %dx%d too large for the banded acting kernel",
+                                 cp.kh, cp.kw);
+        }
+        ActLargeLayout y;
+        act_large_layout(net, np, a, 1, y);
+        if (y.tail.L >= 1 && act_rows_per_block(1, y.tail.ld) == 0)
+            return set_error(DQNX_EUNSUPPORTED, "dqnx_act: layer width %d does not fit LDS", y.tail.ld);
+        a.large = 1;
     }
     return DQNX_OK;
 }
@@ -4289,6 +4365,12 @@ uint64_t dqnx_act_scratch_bytes(const dqnx_net_desc* net, int32_t n) {
     ActArgs a;
     if (act_plan(net, &npp, a)) return 0;
     const NetPlan& np = *npp;
+    if (a.large) {   // one chunk's intermediates + the MLP kernel's part for layers 2..L (never zero for n > 0)
+        if (n <= 0) return 0;
+        ActLargeLayout y;
+        act_large_layout(net, np, a, n, y);
+        return y.bytes + std::max<uint64_t>(y.mlp, 16);
+    }
     const uint64_t mlp = act_scratch_bytes(n, a.out[0], a.ld, a.L, a.L >= 2 ? a.out[1] : 0);
     if (!mlp) return 0;
     return (net->kind == DQNX_NET_MLP ? 0 : act_conv_scratch_bytes(np, n, a.D)) + mlp;
@@ -4300,6 +4382,11 @@ int dqnx_act_kernel_count(const dqnx_net_desc* net, int32_t n, int32_t* count) {
     ActArgs a;
     const int rc = act_plan(net, &npp, a);
     if (rc) return rc;
+    if (a.large) {   // per chunk of kActWideRows rows: a launch per conv, dense 1, its reduce, the rest of the net
+        const int32_t chunks = std::max(1, (n + kActWideRows - 1) / kActWideRows);
+        *count = chunks * ((int32_t)npp->conv.size() + 3);
+        return DQNX_OK;
+    }
     if (act_rows_per_block(std::max(n, 1), a.ld) == 0)
         return set_error(DQNX_EUNSUPPORTED, "dqnx_act: layer width %d does not fit LDS", a.ld);
     ActStackArgs sa;
@@ -4312,11 +4399,11 @@ int dqnx_act_kernel_count(const dqnx_net_desc* net, int32_t n, int32_t* count) {
 // calls) and polls a completion word: MLP nets, and two-stream nets on the one-launch conv stack with one
 // row group (several row groups would each re-read their rows over the host link G times, and store no word)
 static bool act_host_direct(const dqnx_net_desc* net, int32_t n) {
-    if (net->kind == DQNX_NET_MLP) return true;
     const NetPlan* npp = nullptr;
     ActArgs a;
     ActStackArgs sa;
-    if (net->kind != DQNX_NET_TWO_STREAM || act_plan(net, &npp, a)) return false;
+    if (net->kind == DQNX_NET_MLP) return act_large_mode() == 0 || act_plan(net, &npp, a) || !a.large;
+    if (net->kind != DQNX_NET_TWO_STREAM || act_plan(net, &npp, a) || a.large) return false;
     return n <= act_rows_per_block(n, a.ld) && act_ts_plan(*npp, n, sa);
 }
 
@@ -4330,6 +4417,76 @@ int dqnx_act(const dqnx_net_desc* net, const float* params, const float* obs, in
     return act_impl(net, params, obs, n, actions, values, scratch, scratch_bytes, stream, nullptr, 0);
 }
 
+// The large route (DQNX_ACT_LARGE; act_large.hip): chunks of at most kActWideRows rows, each a launch per
+// conv (banded), dense 1 (split-K weight stream), its reduce, and the rest of the net on h1 -- the MLP
+// acting kernel with the layer tables shifted by one, or the head kernel of a one-dense-layer net.  The
+// chunks reuse the scratch in stream order.  Never stores a completion word (act_host_direct says no).
+static int act_large_impl(const dqnx_net_desc* net, const NetPlan& np, const ActArgs& a, const float* params,
+                          const float* obs, int32_t n, int32_t* actions, float* values, void* scratch,
+                          uint64_t scratch_bytes, void* stream) {
+    if (n == 0) return DQNX_OK;
+    const uint64_t need = dqnx_act_scratch_bytes(net, n);
+    if (scratch_bytes < need || (scratch_bytes & 3) || ((uintptr_t)scratch & 15))
+        return set_error(DQNX_EINVAL, "dqnx_act: scratch of %llu bytes too small or misaligned for n=%d",
+                         (unsigned long long)scratch_bytes, n);
+    ActLargeLayout y;
+    act_large_layout(net, np, a, n, y);
+    char* sc = (char*)scratch;
+    hipStream_t s = (hipStream_t)stream;
+    const int NC = (int)np.conv.size();
+    float* F = (float*)(sc + y.F_off);
+    for (int row0 = 0; row0 < n; row0 += kActWideRows) {
+        const int nr = std::min(kActWideRows, n - row0);
+        const float* orow = obs + (int64_t)row0 * net->obs_dim;
+        const float* in = orow;
+        int64_t in_stride = net->obs_dim;
+        int in_off = np.macro_len;   // the micro grid viewed as (c, h, w) (R:env/dqn_config.py:126-128)
+        char* cur = sc;
+        for (int l = 0; l < NC; l++) {
+            const ConvPlan& cp = np.conv[l];
+            ActConvArgs ca;
+            act_conv_args(cp, ca);
+            ca.in = in; ca.in_stride = in_stride; ca.in_off = in_off;
+            ca.W = params + cp.off; ca.b = ca.W + (int64_t)cp.Co * cp.K;
+            ca.n = nr;
+            if (l + 1 < NC) {
+                ca.out = (float*)cur;
+                ca.out_stride = (int64_t)cp.Co * cp.Ho * cp.Wo;
+                cur += (uint64_t)y.Rc * ca.out_stride * 4;
+            } else {   // flatten(conv) ++ macro = the dense input F (R:env/dqn_config.py:135-138)
+                ca.out = F;
+                ca.out_stride = a.D;
+                ca.macro = orow;
+                ca.macro_stride = net->obs_dim;
+                ca.macro_len = np.macro_len;
+            }
+            const int rc = launch_act_conv_band(ca, net->activation, s);
+            if (rc) return rc;
+            in = ca.out; in_stride = ca.out_stride; in_off = 0;
+        }
+        ActWideArgs wa;
+        memset(&wa, 0, sizeof(wa));
+        wa.W = params + a.off[0]; wa.b = wa.W + (int64_t)a.out[0] * a.D;
+        wa.x = NC ? F : orow; wa.x_stride = a.D;
+        wa.part = (float*)(sc + y.part_off); wa.h = (float*)(sc + y.h_off);
+        wa.nr = nr; wa.K = a.D; wa.J = a.out[0]; wa.act = a.act;
+        int rc = launch_act_dense_wide(wa, s);
+        if (rc) return rc;
+        ActArgs t = y.tail;
+        t.params = params; t.obs = wa.h; t.n = nr;
+        t.actions = actions + row0;
+        t.values = values ? values + (int64_t)row0 * a.A : nullptr;
+        t.done_flag = nullptr; t.done_seq = 0;
+        // the MLP kernel's activations after the chunk's intermediates, its tickets at the END of the
+        // caller's buffer: the same address whatever n the buffer serves
+        t.scratch = (float*)(sc + y.bytes);
+        t.tickets = (uint32_t*)(sc + scratch_bytes) - 1;
+        rc = t.L >= 1 ? launch_act(t, s) : launch_act_large_head(t, s);
+        if (rc) return rc;
+    }
+    return DQNX_OK;
+}
+
 static int act_impl(const dqnx_net_desc* net, const float* params, const float* obs, int32_t n, int32_t* actions,
                     float* values, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t* done_flag,
                     uint32_t done_seq, bool* signals) {
@@ -4341,6 +4498,7 @@ static int act_impl(const dqnx_net_desc* net, const float* params, const float* 
     const NetPlan& np = *npp;
     if (n < 0 || (n > 0 && (!params || !obs || !actions || !scratch)))
         return set_error(DQNX_EINVAL, "dqnx_act: bad argument");
+    if (a.large) return act_large_impl(net, np, a, params, obs, n, actions, values, scratch, scratch_bytes, stream);
     const int R = n > 0 ? act_rows_per_block(n, a.ld) : 1;
     if (R == 0) return set_error(DQNX_EUNSUPPORTED, "dqnx_act: layer width %d does not fit LDS", a.ld);
     a.params = params; a.obs = obs; a.actions = actions; a.values = values; a.n = n;

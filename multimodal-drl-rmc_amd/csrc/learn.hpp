@@ -810,6 +810,7 @@ struct ActArgs {
     // host polls it instead of synchronising the stream (null: no flag)
     uint32_t* done_flag;
     uint32_t done_seq;
+    int large;   // the plan takes the large route (DQNX_ACT_LARGE; act_large.hip): host side only
 };
 // two-stream acting: one conv layer over n rows (act_hybrid.hip); images CHW, rows strided
 struct ActConvArgs {
@@ -842,6 +843,27 @@ int launch_act_conv_stack(const ActStackArgs& a, hipStream_t s);
 int act_rows_per_block(int n, int ld);
 uint64_t act_scratch_bytes(int n, int h0, int ld, int L, int out1);
 int launch_act(const ActArgs& a, hipStream_t s);
+// acting path for nets that do not fit LDS (act_large.hip; DQNX_ACT_LARGE): banded convs, dense 1 as a
+// weight-streaming split-K GEMV over chunks of at most kActWideRows rows, its reduce, the head of a
+// one-dense-layer net
+constexpr int kActWideRows = 8;
+struct ActBandPlan {
+    int TW, BH, CiC;   // output tile (columns x rows) of a workgroup, input channels staged at a time
+    size_t lds;
+};
+bool act_band_plan(const ActConvArgs& a, ActBandPlan& p);
+int launch_act_conv_band(const ActConvArgs& a, int act, hipStream_t s);
+struct ActWideArgs {
+    const float* W;   const float* b;          // dense 1: [J][K], [J]
+    const float* x;   int64_t x_stride;        // the chunk's rows
+    float* part;                               // [S][nr][J] split-K shares
+    float* h;                                  // [nr][J] = act(W x + b)
+    int nr, K, J, act;
+    int S, Ls;                                 // (filled by the launch: act_wide_slices)
+};
+void act_wide_slices(int K, int* S, int* Ls);
+int launch_act_dense_wide(const ActWideArgs& a, hipStream_t s);   // two launches: the GEMV, the reduce
+int launch_act_large_head(const ActArgs& a, hipStream_t s);       // head + argmax on obs = h1 [n][F]
 int launch_soft_update(float* target, const float* p, int64_t n, float tau, float omt, hipStream_t s);
 int launch_copy_i32x2(int32_t* d0, const int32_t* s0, int n0, int32_t* d1, const int32_t* s1, int n1, hipStream_t s);
 int launch_replay_push(const PushArgs& a, hipStream_t s);

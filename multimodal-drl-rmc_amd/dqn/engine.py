@@ -168,7 +168,9 @@ def act_scratch(spec: NetSpec, n: int, device) -> torch.Tensor:
 
 def act_supported(spec: NetSpec) -> bool:
     """dqnx_act implements this network (MLP bodies; two-stream bodies whose conv inputs fit the
-    acting kernel's LDS, e.g. the reference's 2x27x5 grid but not the 4x84x84 variant)."""
+    acting kernel's LDS, e.g. the reference's 2x27x5 grid but not the 4x84x84 variant; with
+    DQNX_ACT_LARGE=1 in the environment those too, on the large route.  Network and Agent objects ask
+    once, at their first acting call: set the knob before it)."""
     return int(C.lib().dqnx_act_scratch_bytes(ctypes.byref(spec.to_c()), 1)) > 0
 
 

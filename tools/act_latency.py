@@ -3,7 +3,12 @@ reference's torch forward (R:dqn/network.py:67-74/110-117) on the same resident 
 
 Prints one JSON line: per-call host wall time (obs from host numpy, actions back to a list,
 as Agent.choose_actions uses it) for both paths, and the device time per dqnx_act launch
-over back-to-back launches on device-resident obs."""
+over back-to-back launches on device-resident obs.
+
+`--net two_stream84` measures the (4,84,84) variant instead (n = 1, 2, 8): with DQNX_ACT_LARGE=1 in the
+environment Network.actions takes the acting path's large route, without it the torch forward (no dqnx_act
+launch to time then: act_launch_device_us is null)."""
+import functools
 import json
 import os
 import sys
@@ -32,6 +37,14 @@ def wall(fn, iters):
 
 def main():
     out = {}
+    if "two_stream84" in sys.argv[1:]:
+        torch.manual_seed(0)
+        conf = functools.partial(hybrid_network_config, micro_chw=(4, 84, 84))
+        net = DuelingDeepQNetwork("cuda:0", 1e-4, conf, Box(14 + 4 * 84 * 84), 8)
+        out["DQNX_ACT_LARGE"] = os.environ.get("DQNX_ACT_LARGE")
+        out["two_stream84"] = measure(net, 14 + 4 * 84 * 84, (1, 2, 8), 200)
+        print(json.dumps(out))
+        return
     for tag, conf in (("mlp284", mlp_network_config), ("two_stream", hybrid_network_config)):
         torch.manual_seed(0)
         net = DuelingDeepQNetwork("cuda:0", 1e-4, conf, Box(284), 8)
@@ -39,10 +52,10 @@ def main():
     print(json.dumps(out))
 
 
-def measure(net):
+def measure(net, obs_dim=284, rows=(1, 2, 8, 64), iters=500):
     out = {}
-    for n in (1, 2, 8, 64):
-        x = np.random.default_rng(n).random((n, 284), dtype=np.float32)
+    for n in rows:
+        x = np.random.default_rng(n).random((n, obs_dim), dtype=np.float32)
         xt = torch.from_numpy(x).cuda()
 
         def torch_path():
@@ -51,6 +64,10 @@ def measure(net):
 
         got, want = net.actions(x), torch_path()
         assert sum(a != b for a, b in zip(got, want)) <= max(1, n // 32), (got, want)   # fp32 near-ties only
+        if net._native_act() is None:   # Network.actions is the torch forward
+            out[f"n{n}"] = {"actions_native_us": wall(lambda: net.actions(x), iters),
+                            "actions_torch_us": wall(torch_path, iters), "act_launch_device_us": None}
+            continue
         spec, flat = net._native_act()
         res = torch.empty(n, dtype=torch.int32, device="cuda")
         scratch, desc = E.act_scratch(spec, n, "cuda"), spec.to_c()
@@ -61,13 +78,13 @@ def measure(net):
         for _ in range(20):
             launch()
         ev0.record()
-        for _ in range(500):
+        for _ in range(iters):
             launch()
         ev1.record()
         torch.cuda.synchronize()
-        out[f"n{n}"] = {"actions_native_us": wall(lambda: net.actions(x), 500),
-                        "actions_torch_us": wall(torch_path, 500),
-                        "act_launch_device_us": ev0.elapsed_time(ev1) * 1e3 / 500}
+        out[f"n{n}"] = {"actions_native_us": wall(lambda: net.actions(x), iters),
+                        "actions_torch_us": wall(torch_path, iters),
+                        "act_launch_device_us": ev0.elapsed_time(ev1) * 1e3 / iters}
         del res
     return out
 
