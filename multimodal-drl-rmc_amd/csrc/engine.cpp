@@ -12,6 +12,7 @@
 #include <cmath>
 #include <functional>
 #include <map>
+#include <memory>
 #include <tuple>
 #include <string>
 #include <vector>
@@ -1458,6 +1459,13 @@ constexpr int KEY_RELAYOUT = 0x40;
 // 0 holds the minibatch the previous step drew); one more workgroup of the forward launch draws the
 // next step's minibatch into the staging slot 1, and the last launch copies it over slot 0
 constexpr int KEY_SAMPLE_NEXT = 0x80;
+// KEY_SLOT1: the step computes on (idx, phys) slot 1 (slot << 8); dqnx_apply_grads' own graph key
+constexpr int KEY_SLOT1 = 0x100;
+// KEY_KEEP_BLK (dqnx_apply_grads): a prefetched minibatch is pending, so no sampler launch comes next
+// and the Adam pass keeps the fused plan's blocked copies itself
+constexpr int KEY_KEEP_BLK = 0x200;
+// KEY_KEEP_MTC (dqnx_apply_grads): the next step's in-forward draw reads its MT blocks from the cache
+constexpr int KEY_KEEP_MTC = 0x400;
 // KEY_AGENT_RNG: the sampler launch draws from the drop-in Agent's pinned state block in place
 // (dqnx_agent_launch, uniform replay) instead of the control block an upload copy filled
 constexpr int KEY_AGENT_RNG = 0x4000;
@@ -1465,7 +1473,7 @@ constexpr int KEY_AGENT_RNG = 0x4000;
 // clipping tail below.  One bit of its own, as DQNX_STEP_STATS is 0x10: no other key changes.
 constexpr int KEY_CLIP = 0x20;
 // KEY_CLIP_TAIL: the launches after the gradient -- grad_sumsq, clip_coef, dqnx_apply_grads' launches with
-// the coefficient (key bits 0x200 / 0x400 as enqueue_apply reads them), then (DQNX_STEP_STATS) the
+// the coefficient (KEY_KEEP_BLK / KEY_KEEP_MTC as enqueue_apply reads them), then (DQNX_STEP_STATS) the
 // statistics launch on slot (key >> 8) & 1
 constexpr int KEY_CLIP_TAIL = 0x8000;
 
@@ -1576,9 +1584,6 @@ static KStep stats_kstep(dqnx_engine* e, int key) {
     return k;
 }
 
-static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key);
-int enqueue_apply(dqnx_engine* e, int flags, hipStream_t s, int parts = 3);
-
 static bool clip_on(const dqnx_engine* e) { return e->grad_clip > 0.0; }
 
 ClipArgs clip_args(dqnx_engine* e) {
@@ -1596,312 +1601,290 @@ ClipArgs clip_args(dqnx_engine* e) {
     return ca;
 }
 
-// The tail of a clipped step (KEY_CLIP_TAIL), and all of a clipped dqnx_apply_grads: the gradient's sum
-// of squares, the coefficient, then dqnx_apply_grads' launches reading it (clip.hip).
-static std::vector<KStep> clip_tail_steps(dqnx_engine* e, int key) {
-    std::vector<KStep> ks;
-    const double P = (double)e->np.P;
-    const ClipArgs ca = clip_args(e);
-    const int akey = (key & (DQNX_STEP_SOFT_UPDATE | 0x200 | 0x400)) | KEY_CLIP;
-    const bool soft = (key & DQNX_STEP_SOFT_UPDATE) != 0;
+// What every builder of a plan key's launch list reads: the engine, the key's parts, the (idx, phys) slot
+// the step computes on, the flat parameter vectors and ring rows, and the sizes the FLOPs / bytes use.
+struct StepCtx {
+    dqnx_engine* e;
+    int key, flags, slot;
+    int32_t *idx, *phys;
+    float *params, *tparams;
+    const float *ring_obs, *ring_next;
+    dqnx_ctrl* ctrl;
+    bool dbl;             // streams 0 online(obs), 1 online(next) [double], 2 target(next)
+    int nstreams, act, L, NC, A;
+    double Bl, Bg;
+};
+
+static StepCtx step_ctx(dqnx_engine* e, int key) {
+    StepCtx cx;
+    cx.e = e;
+    cx.key = key;
+    cx.flags = key & 0x3f;
+    cx.slot = (key >> 8) & 1;
+    cx.idx = at<int32_t>(e, e->off[DQNX_BUF_BATCH_IDX]) + (size_t)cx.slot * e->Bg;
+    cx.phys = at<int32_t>(e, e->ws_phys) + (size_t)cx.slot * e->Bl;
+    cx.params = at<float>(e, e->off[DQNX_BUF_PARAMS]);
+    cx.tparams = at<float>(e, e->off[DQNX_BUF_TARGET_PARAMS]);
+    cx.ring_obs = at<float>(e, e->off[DQNX_BUF_RING_OBS]);
+    cx.ring_next = at<float>(e, e->off[DQNX_BUF_RING_NEXT_OBS]);
+    cx.ctrl = ctrl_of(e);
+    cx.dbl = e->cfg.algo != DQNX_ALGO_DQN;
+    cx.nstreams = cx.dbl ? 3 : 2;
+    cx.act = e->cfg.net.activation;
+    cx.L = (int)e->np.dense.size();
+    cx.NC = (int)e->np.conv.size();
+    cx.A = e->cfg.net.n_actions;
+    cx.Bl = e->Bl;
+    cx.Bg = e->Bg;
+    return cx;
+}
+
+// one launch of the list
+static void push(std::vector<KStep>& ks, const std::string& name, double flops, double bytes,
+                 std::function<int(hipStream_t)> run) {
     KStep k;
-    k.name = "grad_sumsq";
-    k.flops = 2.0 * P;
-    k.bytes = 4.0 * P + 8.0 * ca.n_part;
-    k.run = [=](hipStream_t s) { return launch_grad_sumsq(ca, s); };
-    ks.push_back(k);
-    k.name = "clip_coef";
-    k.flops = 0;
-    k.bytes = 8.0 * ca.n_part + sizeof(dqnx_grad_clip_info);
-    k.run = [=](hipStream_t s) { return launch_clip_coef(ca, s); };
-    ks.push_back(k);
-    if (e->cfg.algo == DQNX_ALGO_PER_DOUBLE) {   // the tree update dqnx_apply_grads makes
-        k.name = "per_update";
-        k.flops = 0;
-        k.bytes = 12.0 * e->Bg;
-        k.run = [=](hipStream_t s) { return enqueue_apply(e, akey, s, 1); };
-        ks.push_back(k);
-    }
-    k.name = "adam_clipped";
-    k.flops = 13.0 * P;   // g * coef, then Adam
-    k.bytes = 4.0 * (7.0 * P + (soft ? 2.0 * P : 0.0));   // read g, p, m, v (+ target); write p, m, v (+ target)
-    k.run = [=](hipStream_t s) {
-        const int rc = enqueue_apply(e, akey, s, 2);
-        if (rc) return rc;
-        // dqnx_apply_grads' bookkeeping, here too so that an eagerly enqueued plan (dqnx_learn_step_timed)
-        // leaves it right: mode 2 changes the conv weights without their permuted copies, and the
-        // fused plan's blocked copies are current only if this pass wrote them
-        e->perm_dirty = true;
-        if (akey & 0x200) e->wblk_dirty = false;
-        else if (!adam_keeps_blk(e)) e->wblk_dirty = true;
-        return rc;
-    };
-    ks.push_back(k);
-    if ((key & DQNX_STEP_STATS) && e->stats_chunks) ks.push_back(stats_kstep(e, key));
-    return ks;
+    k.name = name;
+    k.flops = flops;
+    k.bytes = bytes;
+    k.run = std::move(run);
+    ks.push_back(std::move(k));
 }
 
-// a step's launches: the compute launches of the plan, then (DQNX_STEP_STATS) the statistics launch
-std::vector<KStep> build_learn_steps(dqnx_engine* e, int key) {
-    if (key & KEY_CLIP_TAIL) return clip_tail_steps(e, key);
-    if (key & KEY_CLIP) {
-        // gradient clipping: the gradient-only plan, then the tail.  With the in-launch draw
-        // (KEY_SAMPLE_NEXT) a minibatch is pending when the Adam pass runs: on the fused plan it
-        // writes the blocked copies itself, as dqnx_apply_grads does then
-        std::vector<KStep> ks =
-            build_compute_steps(e, (key & ~(KEY_CLIP | DQNX_STEP_STATS | DQNX_STEP_SOFT_UPDATE)) | DQNX_STEP_GRADS_ONLY);
-        const bool keep = e->bwd_plan == 2 && (key & KEY_SAMPLE_NEXT);
-        const std::vector<KStep> tail = clip_tail_steps(
-            e, KEY_CLIP_TAIL | (key & (DQNX_STEP_SOFT_UPDATE | DQNX_STEP_STATS | 0x100)) | (keep ? 0x600 : 0));
-        ks.insert(ks.end(), tail.begin(), tail.end());
-        return ks;
+// fn(z, st) for every active stream st -- {0, 2} for DQN, {0, 1, 2} otherwise -- with its compact index z;
+// returns their number
+template <class Fn>
+static int for_streams(bool dbl, Fn fn) {
+    int z = 0;
+    for (int st = 0; st < 3; st++) {
+        if (st == 1 && !dbl) continue;
+        fn(z++, st);
     }
-    std::vector<KStep> ks = build_compute_steps(e, key & ~DQNX_STEP_STATS);
-    if ((key & DQNX_STEP_STATS) && e->stats_chunks) ks.push_back(stats_kstep(e, key));
-    return ks;
+    return z;
 }
 
-static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
-    const int flags = key & 0x3f;
-    const int slot = (key >> 8) & 1;
-    std::vector<KStep> ks;
+// the staging slot's sampler arguments (in-launch prefetch; the compute slot is slot 0)
+static SampleArgs staging_sample_args(dqnx_engine* e) {
+    return uniform_sample_args(e, at<int32_t>(e, e->off[DQNX_BUF_BATCH_IDX]) + (size_t)e->Bg,
+                               at<int32_t>(e, e->ws_phys) + (size_t)e->Bl);
+}
+
+// 3b. PER priorities (R:dqn/agent.py:263-265): single GPU here; under DP after the
+//     all-gather of |delta|, in dqnx_apply_grads
+static void per_update_step(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    const int32_t* idx = cx.idx;
+    push(ks, "per_update", 0, cx.Bg * (4.0 + 4.0 + 8.0 * 2.0 * 21.0),
+         [=](hipStream_t s) { return enqueue_per_update(e, idx, s); });
+}
+
+// the fused MLP plan's launches (build_fused_steps), with the staging slot's sampler under KEY_SAMPLE_NEXT
+static void fused_steps(const StepCtx& cx, std::vector<KStep>& ks) {
+    SampleArgs nxt;
+    const bool sample_next = (cx.key & KEY_SAMPLE_NEXT) != 0;
+    if (sample_next) nxt = staging_sample_args(cx.e);
+    build_fused_steps(cx.e, cx.flags, cx.idx, cx.phys, ks, sample_next ? &nxt : nullptr);
+}
+
+// 1. sample (R:dqn/replay_memory.py:38-39; PER :69-92)
+// (none under KEY_SAMPLE_NEXT: slot 0 holds the minibatch the previous step drew)
+static void sample_steps(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
     const dqnx_config& c = e->cfg;
-    const NetPlan& np = e->np;
-    const int L = (int)np.dense.size();
-    const int A = c.net.n_actions;
-    const int act = c.net.activation;
-    dqnx_ctrl* ctrl = ctrl_of(e);
-    float* params = at<float>(e, e->off[DQNX_BUF_PARAMS]);
-    float* tparams = at<float>(e, e->off[DQNX_BUF_TARGET_PARAMS]);
-    int32_t* idx = at<int32_t>(e, e->off[DQNX_BUF_BATCH_IDX]) + (size_t)slot * e->Bg;
-    int32_t* phys = at<int32_t>(e, e->ws_phys) + (size_t)slot * e->Bl;
-    const double Bl = e->Bl;
-    const double Bg_ = e->Bg;
-
-    // 1. sample (R:dqn/replay_memory.py:38-39; PER :69-92)
     int rl_blocks = 0;
     RelayoutArgs rl = relayout_args(e, &rl_blocks);
-    if (!(key & KEY_RELAYOUT)) {
+    if (!(cx.key & KEY_RELAYOUT)) {
         rl.njobs = 0;
         rl.total_q = 0;
         rl_blocks = 0;
     }
     if (c.algo == DQNX_ALGO_PER_DOUBLE) {
-        PerSampleArgs pa = per_sample_args(e, idx, phys);
+        PerSampleArgs pa = per_sample_args(e, cx.idx, cx.phys);
         pa.rl = rl;
         pa.rl_blocks = rl_blocks;
-        KStep k;
-        k.name = "per_sample";
-        k.bytes = 2.0 * 625 * 4 + 8.0 * Bg_ * 22 + 8.0 * e->Bg + 4.0 * Bl;
-        k.run = [=](hipStream_t s) { return launch_per_sample(pa, s); };
-        ks.push_back(k);
-    } else if (flags & DQNX_STEP_GIVEN_INDICES) {
-        KStep k;
-        k.name = "idx_to_phys";
-        k.bytes = 8.0 * Bl;
-        k.run = [=](hipStream_t s) {
-            return launch_idx_to_phys(idx, phys, e->shard_begin, e->Bl, ctrl, c.capacity, &rl, rl_blocks, s);
-        };
-        ks.push_back(k);
-    } else if (!(key & KEY_SAMPLE_NEXT)) {
-        SampleArgs sa = uniform_sample_args(e, idx, phys);
+        push(ks, "per_sample", 0, 2.0 * 625 * 4 + 8.0 * cx.Bg * 22 + 8.0 * e->Bg + 4.0 * cx.Bl,
+             [=](hipStream_t s) { return launch_per_sample(pa, s); });
+    } else if (cx.flags & DQNX_STEP_GIVEN_INDICES) {
+        int32_t *idx = cx.idx, *phys = cx.phys;
+        dqnx_ctrl* ctrl = cx.ctrl;
+        push(ks, "idx_to_phys", 0, 8.0 * cx.Bl, [=](hipStream_t s) {
+            return launch_idx_to_phys(idx, phys, e->shard_begin, e->Bl, ctrl, e->cfg.capacity, &rl, rl_blocks, s);
+        });
+    } else if (!(cx.key & KEY_SAMPLE_NEXT)) {
+        SampleArgs sa = uniform_sample_args(e, cx.idx, cx.phys);
         sa.rl = rl;
         sa.rl_blocks = rl_blocks;
-        if (key & KEY_AGENT_RNG) sa.state_in = e->ag_rng_zc;
-        KStep k;
-        k.name = "sample_uniform";
-        k.bytes = 2.0 * 625 * 4 + 4.0 * e->Bs + 4.0 * Bl;
-        k.run = [=](hipStream_t s) { return launch_sample_uniform(sa, s); };
-        ks.push_back(k);
+        if (cx.key & KEY_AGENT_RNG) sa.state_in = e->ag_rng_zc;
+        push(ks, "sample_uniform", 0, 2.0 * 625 * 4 + 4.0 * e->Bs + 4.0 * cx.Bl,
+             [=](hipStream_t s) { return launch_sample_uniform(sa, s); });
     }
+}
 
-    if (e->bwd_plan == 2) {
-        SampleArgs nxt;
-        const bool sample_next = (key & KEY_SAMPLE_NEXT) != 0;
-        if (sample_next)   // the staging slot (the compute slot is slot 0)
-            nxt = uniform_sample_args(e, at<int32_t>(e, e->off[DQNX_BUF_BATCH_IDX]) + (size_t)e->Bg,
-                                      at<int32_t>(e, e->ws_phys) + (size_t)e->Bl);
-        build_fused_steps(e, flags, idx, phys, ks, sample_next ? &nxt : nullptr);
-        return ks;
+// 2a'. implicit-GEMM convs, the last one writing F (conv_ig.hip)
+static void conv_ig_fwd(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    const NetPlan& np = e->np;
+    const int act = cx.act;
+    ConvPermArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    double pbytes = 0;
+    for (int l = 0; l < cx.NC; l++) {
+        const ConvPlan& cp = np.conv[l];
+        const int taps = cp.kh * cp.kw;
+        pa.job[pa.njobs++] = ConvPermJob{cx.params + cp.off, at<float>(e, e->ws_wperm0[l]), cp.Co, cp.Ci, taps, 0};
+        pa.job[pa.njobs++] = ConvPermJob{cx.tparams + cp.off, at<float>(e, e->ws_wperm1[l]), cp.Co, cp.Ci, taps, 0};
+        if (l > 0) pa.job[pa.njobs++] = ConvPermJob{cx.params + cp.off, at<float>(e, e->ws_wpermT[l]), cp.Co, cp.Ci, taps, 1};
+        pbytes += 8.0 * cp.Co * cp.K * (l > 0 ? 3 : 2);
     }
+    push(ks, "conv_perm", 0, pbytes, [=](hipStream_t s) { return launch_conv_perm(pa, s); });
+    for (int l = 0; l < cx.NC; l++) {
+        const ConvPlan cp = np.conv[l];
+        const bool last = l == cx.NC - 1;
+        ConvIgArgs ca;
+        cig_fwd_geom(cp, e->Bl, l == 0, ca);
+        ca.act = act;
+        CigSource& S = ca.src;
+        if (l == 0) {   // the micro grid straight from the ring rows (CHW after the macro features)
+            S.phys = cx.phys;
+            S.bstride = e->stride;
+            S.off = np.macro_len;
+            S.pstride = 1;
+            S.cstride = cp.Hi * cp.Wi;
+        } else {
+            S.bstride = (int64_t)cp.Hi * cp.Wi * cp.Ci;
+            S.pstride = cp.Ci;
+            S.cstride = 1;
+        }
+        ca.nstreams = for_streams(cx.dbl, [&](int z, int st) {
+            S.base[z] = l == 0 ? (st == 0 ? cx.ring_obs : cx.ring_next)
+                               : at<float>(e, e->ws_Hc[l - 1]) + (int64_t)st * e->Bl * cp.Hi * cp.Wi * cp.Ci;
+            ca.W[z] = at<float>(e, st == 2 ? e->ws_wperm1[l] : e->ws_wperm0[l]);
+            ca.bias[z] = (st == 2 ? cx.tparams : cx.params) + cp.off + (int64_t)cp.Co * cp.K;
+            if (last) {
+                ca.out[z] = at<float>(e, e->ws_F) + (int64_t)st * e->Bl * np.strideF;
+                ca.ring[z] = st == 0 ? cx.ring_obs : cx.ring_next;
+            } else {
+                ca.out[z] = at<float>(e, e->ws_Hc[l]) + (int64_t)st * e->Bl * cp.Ho * cp.Wo * cp.Co;
+            }
+        });
+        if (last) {   // F[b] = cat(flatten_CHW(conv), macro) (R:env/dqn_config.py:135-138)
+            ca.ob = np.strideF;
+            ca.orow = cp.Wo;
+            ca.opix = 1;
+            ca.och = cp.Ho * cp.Wo;
+            ca.phys = cx.phys;
+            ca.ring_stride = e->stride;
+            ca.macro_len = np.macro_len;
+            ca.flat_cols = cp.Co * cp.Ho * cp.Wo;
+            ca.strideF = np.strideF;
+        } else {
+            ca.ob = (int64_t)cp.Ho * cp.Wo * cp.Co;
+            ca.orow = cp.Wo * cp.Co;
+            ca.opix = cp.Co;
+            ca.och = 1;
+        }
+        const double M = (double)e->Bl * cp.Ho * cp.Wo;
+        const int epi = last ? CIG_EPI_FLAT : CIG_EPI_NHWC;
+        push(ks, "conv_fwd_c" + std::to_string(l + 1),
+             /*flops*/ 2.0 * cx.nstreams * M * cp.Co * cp.K,
+             /*bytes*/ 4.0 * (cx.nstreams * (cx.Bl * (double)cp.Ci * cp.Hi * cp.Wi + M * cp.Co) + 2.0 * cp.Co * (cp.K + 1.0)),
+             [=](hipStream_t s) { return launch_conv_ig(ca, epi, s); });
+    }
+}
 
-    // 2. forward layers: streams 0 online(obs), 1 online(next) [double], 2 target(next)
-    const bool dbl = c.algo != DQNX_ALGO_DQN;
-    const int nstreams = dbl ? 3 : 2;
-    const int NC = (int)np.conv.size();
-    const float* ring_obs = at<float>(e, e->off[DQNX_BUF_RING_OBS]);
-    const float* ring_next = at<float>(e, e->off[DQNX_BUF_RING_NEXT_OBS]);
-    if (NC && e->conv_ig) {   // 2a'. implicit-GEMM convs, the last one writing F (conv_ig.hip)
-        ConvPermArgs pa;
-        memset(&pa, 0, sizeof(pa));
-        double pbytes = 0;
-        for (int l = 0; l < NC; l++) {
-            const ConvPlan& cp = np.conv[l];
-            const int taps = cp.kh * cp.kw;
-            pa.job[pa.njobs++] = ConvPermJob{params + cp.off, at<float>(e, e->ws_wperm0[l]), cp.Co, cp.Ci, taps, 0};
-            pa.job[pa.njobs++] = ConvPermJob{tparams + cp.off, at<float>(e, e->ws_wperm1[l]), cp.Co, cp.Ci, taps, 0};
-            if (l > 0) pa.job[pa.njobs++] = ConvPermJob{params + cp.off, at<float>(e, e->ws_wpermT[l]), cp.Co, cp.Ci, taps, 1};
-            pbytes += 8.0 * cp.Co * cp.K * (l > 0 ? 3 : 2);
-        }
-        {
-            KStep k;
-            k.name = "conv_perm";
-            k.bytes = pbytes;
-            k.run = [=](hipStream_t s) { return launch_conv_perm(pa, s); };
-            ks.push_back(k);
-        }
-        for (int l = 0; l < NC; l++) {
-            const ConvPlan cp = np.conv[l];
-            const bool last = l == NC - 1;
-            ConvIgArgs ca;
-            cig_fwd_geom(cp, e->Bl, l == 0, ca);
-            ca.act = act;
-            CigSource& S = ca.src;
-            if (l == 0) {   // the micro grid straight from the ring rows (CHW after the macro features)
-                S.phys = phys;
-                S.bstride = e->stride;
-                S.off = np.macro_len;
-                S.pstride = 1;
-                S.cstride = cp.Hi * cp.Wi;
-            } else {
-                S.bstride = (int64_t)cp.Hi * cp.Wi * cp.Ci;
-                S.pstride = cp.Ci;
-                S.cstride = 1;
-            }
-            int z = 0;
-            for (int st = 0; st < 3; st++) {
-                if (st == 1 && !dbl) continue;
-                S.base[z] = l == 0 ? (st == 0 ? ring_obs : ring_next)
-                                   : at<float>(e, e->ws_Hc[l - 1]) + (int64_t)st * e->Bl * cp.Hi * cp.Wi * cp.Ci;
-                ca.W[z] = at<float>(e, st == 2 ? e->ws_wperm1[l] : e->ws_wperm0[l]);
-                ca.bias[z] = (st == 2 ? tparams : params) + cp.off + (int64_t)cp.Co * cp.K;
-                if (last) {
-                    ca.out[z] = at<float>(e, e->ws_F) + (int64_t)st * e->Bl * np.strideF;
-                    ca.ring[z] = st == 0 ? ring_obs : ring_next;
-                } else {
-                    ca.out[z] = at<float>(e, e->ws_Hc[l]) + (int64_t)st * e->Bl * cp.Ho * cp.Wo * cp.Co;
-                }
-                z++;
-            }
-            ca.nstreams = z;
-            if (last) {   // F[b] = cat(flatten_CHW(conv), macro) (R:env/dqn_config.py:135-138)
-                ca.ob = np.strideF;
-                ca.orow = cp.Wo;
-                ca.opix = 1;
-                ca.och = cp.Ho * cp.Wo;
-                ca.phys = phys;
-                ca.ring_stride = e->stride;
-                ca.macro_len = np.macro_len;
-                ca.flat_cols = cp.Co * cp.Ho * cp.Wo;
-                ca.strideF = np.strideF;
-            } else {
-                ca.ob = (int64_t)cp.Ho * cp.Wo * cp.Co;
-                ca.orow = cp.Wo * cp.Co;
-                ca.opix = cp.Co;
-                ca.och = 1;
-            }
-            const double M = (double)e->Bl * cp.Ho * cp.Wo;
-            KStep k;
-            k.name = "conv_fwd_c" + std::to_string(l + 1);
-            k.flops = 2.0 * nstreams * M * cp.Co * cp.K;
-            k.bytes = 4.0 * (nstreams * (Bl * (double)cp.Ci * cp.Hi * cp.Wi + M * cp.Co) + 2.0 * cp.Co * (cp.K + 1.0));
-            const int epi = last ? CIG_EPI_FLAT : CIG_EPI_NHWC;
-            k.run = [=](hipStream_t s) { return launch_conv_ig(ca, epi, s); };
-            ks.push_back(k);
-        }
+// The micro-CNN plan's convs as its kernels read them (micro.hip): the geometry with the forward's LDS
+// layout (x0, zero, if asked for: its input and zero-pad offsets), and this engine's permuted weight copies
+// (convs 2..: conv 1 reads the torch layout directly), stream-0 activations and dZ
+static void micro_convs(dqnx_engine* e, MicroConv* mconv, int* x0 = nullptr, int* zero = nullptr) {
+    const int NC = (int)e->np.conv.size();
+    int x0_ = 0, zero_ = 0;
+    micro_geom(e->np, mconv);
+    micro_fwd_layout(mconv, NC, e->micro_S, x0 ? x0 : &x0_, zero ? zero : &zero_);
+    for (int l = 1; l < NC; l++) {
+        mconv[l].wp[0] = at<float>(e, e->ws_wperm0[l]);
+        mconv[l].wp[1] = at<float>(e, e->ws_wperm1[l]);
+        mconv[l].wT = at<float>(e, e->ws_wpermT[l]);
     }
-    // micro-CNN plan: conv weights of the step in the kernels' layouts, then ONE launch for every
-    // conv of every stream (micro.hip)
-    MicroConv mconv[MICRO_MAX_CONV];
-    if (NC && e->micro) {
-        micro_geom(np, mconv);
-        int x0 = 0, zero = 0;
-        micro_fwd_layout(mconv, NC, e->micro_S, &x0, &zero);
-        ConvPermArgs pa;
-        memset(&pa, 0, sizeof(pa));
-        double pbytes = 0;
-        for (int l = 1; l < NC; l++) {   // conv 1 reads the torch layout directly
-            const ConvPlan& cp = np.conv[l];
-            pa.job[pa.njobs++] = ConvPermJob{params + cp.off, at<float>(e, e->ws_wperm0[l]), cp.Co, cp.Ci, 9, 0};
-            pa.job[pa.njobs++] = ConvPermJob{tparams + cp.off, at<float>(e, e->ws_wperm1[l]), cp.Co, cp.Ci, 9, 0};
-            pa.job[pa.njobs++] = ConvPermJob{params + cp.off, at<float>(e, e->ws_wpermT[l]), cp.Co, cp.Ci, 9, 1};
-            mconv[l].wp[0] = at<float>(e, e->ws_wperm0[l]);
-            mconv[l].wp[1] = at<float>(e, e->ws_wperm1[l]);
-            mconv[l].wT = at<float>(e, e->ws_wpermT[l]);
-            pbytes += 8.0 * cp.Co * cp.K * 3;
-        }
-        for (int l = 0; l < NC; l++) {
-            mconv[l].hc = l + 1 < NC ? at<float>(e, e->ws_Hc[l]) : nullptr;
-            mconv[l].dz = at<float>(e, e->ws_dZc[l]);
-        }
-        {
-            KStep k;
-            k.name = "conv_perm";
-            k.bytes = pbytes;
-            // eager: only while the copies are stale (the last step's Adam pass wrote them otherwise);
-            // a captured graph always holds the launch (its replays may follow any update)
-            k.run = [=](hipStream_t s) {
-                hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-                DQNX_HIP_CHECK(hipStreamIsCapturing(s, &cs));
-                if (!e->perm_dirty && cs == hipStreamCaptureStatusNone) return (int)DQNX_OK;
-                return launch_conv_perm(pa, s);
-            };
-            ks.push_back(k);
-        }
-        MicroFwdArgs ma;
-        memset(&ma, 0, sizeof(ma));
-        for (int l = 0; l < NC; l++) ma.c[l] = mconv[l];
-        ma.nc = NC;
-        ma.Bl = e->Bl;
-        ma.S = e->micro_S;
-        ma.groups = (e->Bl + ma.S - 1) / ma.S;
-        int z = 0;
-        for (int st = 0; st < 3; st++) {
-            if (st == 1 && !dbl) continue;
-            ma.stream_of[z] = st;
-            ma.F[z] = at<float>(e, e->ws_F) + (int64_t)st * e->Bl * np.strideF;
-            z++;
-        }
-        ma.nstreams = z;
-        ma.params = params;
-        ma.tparams = tparams;
-        ma.ring_obs = ring_obs;
-        ma.ring_next = ring_next;
-        ma.ring_stride = e->stride;
-        ma.macro_len = np.macro_len;
-        ma.phys = phys;
-        ma.strideF = np.strideF;
-        const ConvPlan& cl = np.conv[NC - 1];
-        ma.flat_cols = cl.Co * cl.Ho * cl.Wo;
-        ma.x0 = x0;
-        ma.zero = zero;
-        ma.lds_floats = e->micro_lds;
-        if (key & KEY_SAMPLE_NEXT) {   // + the next step's minibatch into the staging slot (in-launch prefetch)
-            ma.samp_on = 1;
-            ma.samp = uniform_sample_args(e, at<int32_t>(e, e->off[DQNX_BUF_BATCH_IDX]) + (size_t)e->Bg,
-                                          at<int32_t>(e, e->ws_phys) + (size_t)e->Bl);
-            ma.samp.stamps = nullptr;
-        }
-#ifdef DQNX_STAMPS
-        ma.stamps = at<int64_t>(e, e->ws_stamps);
-#endif
-        double flops = 0, bytes = 0;
-        for (int l = 0; l < NC; l++) {
-            const ConvPlan& cp = np.conv[l];
-            flops += 2.0 * nstreams * Bl * cp.Ho * cp.Wo * (double)cp.Co * cp.K;
-            bytes += 4.0 * 2.0 * (cp.Co * (double)cp.K + cp.Co) + (l + 1 < NC ? 4.0 * Bl * cp.Ho * cp.Wo * cp.Co : 0.0);
-        }
-        bytes += 4.0 * nstreams * Bl * (np.conv[0].Ci * np.conv[0].Hi * np.conv[0].Wi + np.strideF);
-        KStep k;
-        k.name = ma.samp_on ? "micro_fwd+sample" : "micro_fwd";
-        k.flops = flops;
-        k.bytes = bytes;
-        k.run = [=](hipStream_t s) { return launch_micro_fwd(ma, s); };
-        ks.push_back(k);
-    }
-    if (!e->conv_ig && !e->micro) {
-    // 2a. two-stream micro CNN (R:env/dqn_config.py:92-101, forward :126-133): im2col + MFMA GEMM
     for (int l = 0; l < NC; l++) {
+        mconv[l].hc = l + 1 < NC ? at<float>(e, e->ws_Hc[l]) : nullptr;
+        mconv[l].dz = at<float>(e, e->ws_dZc[l]);
+    }
+}
+
+// micro-CNN plan: conv weights of the step in the kernels' layouts, then ONE launch for every
+// conv of every stream (micro.hip)
+static void conv_micro_fwd(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    const NetPlan& np = e->np;
+    MicroConv mconv[MICRO_MAX_CONV];
+    int x0 = 0, zero = 0;
+    micro_convs(e, mconv, &x0, &zero);
+    ConvPermArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    double pbytes = 0;
+    for (int l = 1; l < cx.NC; l++) {   // conv 1 reads the torch layout directly
+        const ConvPlan& cp = np.conv[l];
+        pa.job[pa.njobs++] = ConvPermJob{cx.params + cp.off, at<float>(e, e->ws_wperm0[l]), cp.Co, cp.Ci, 9, 0};
+        pa.job[pa.njobs++] = ConvPermJob{cx.tparams + cp.off, at<float>(e, e->ws_wperm1[l]), cp.Co, cp.Ci, 9, 0};
+        pa.job[pa.njobs++] = ConvPermJob{cx.params + cp.off, at<float>(e, e->ws_wpermT[l]), cp.Co, cp.Ci, 9, 1};
+        pbytes += 8.0 * cp.Co * cp.K * 3;
+    }
+    // eager: only while the copies are stale (the last step's Adam pass wrote them otherwise);
+    // a captured graph always holds the launch (its replays may follow any update)
+    push(ks, "conv_perm", 0, pbytes, [=](hipStream_t s) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        DQNX_HIP_CHECK(hipStreamIsCapturing(s, &cs));
+        if (!e->perm_dirty && cs == hipStreamCaptureStatusNone) return (int)DQNX_OK;
+        return launch_conv_perm(pa, s);
+    });
+    MicroFwdArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    for (int l = 0; l < cx.NC; l++) ma.c[l] = mconv[l];
+    ma.nc = cx.NC;
+    ma.Bl = e->Bl;
+    ma.S = e->micro_S;
+    ma.groups = (e->Bl + ma.S - 1) / ma.S;
+    ma.nstreams = for_streams(cx.dbl, [&](int z, int st) {
+        ma.stream_of[z] = st;
+        ma.F[z] = at<float>(e, e->ws_F) + (int64_t)st * e->Bl * np.strideF;
+    });
+    ma.params = cx.params;
+    ma.tparams = cx.tparams;
+    ma.ring_obs = cx.ring_obs;
+    ma.ring_next = cx.ring_next;
+    ma.ring_stride = e->stride;
+    ma.macro_len = np.macro_len;
+    ma.phys = cx.phys;
+    ma.strideF = np.strideF;
+    const ConvPlan& cl = np.conv[cx.NC - 1];
+    ma.flat_cols = cl.Co * cl.Ho * cl.Wo;
+    ma.x0 = x0;
+    ma.zero = zero;
+    ma.lds_floats = e->micro_lds;
+    if (cx.key & KEY_SAMPLE_NEXT) {   // + the next step's minibatch into the staging slot (in-launch prefetch)
+        ma.samp_on = 1;
+        ma.samp = staging_sample_args(e);
+        ma.samp.stamps = nullptr;
+    }
+#ifdef DQNX_STAMPS
+    ma.stamps = at<int64_t>(e, e->ws_stamps);
+#endif
+    double flops = 0, bytes = 0;
+    for (int l = 0; l < cx.NC; l++) {
+        const ConvPlan& cp = np.conv[l];
+        flops += 2.0 * cx.nstreams * cx.Bl * cp.Ho * cp.Wo * (double)cp.Co * cp.K;
+        bytes += 4.0 * 2.0 * (cp.Co * (double)cp.K + cp.Co) + (l + 1 < cx.NC ? 4.0 * cx.Bl * cp.Ho * cp.Wo * cp.Co : 0.0);
+    }
+    bytes += 4.0 * cx.nstreams * cx.Bl * (np.conv[0].Ci * np.conv[0].Hi * np.conv[0].Wi + np.strideF);
+    push(ks, ma.samp_on ? "micro_fwd+sample" : "micro_fwd", flops, bytes,
+         [=](hipStream_t s) { return launch_micro_fwd(ma, s); });
+}
+
+// 2a. two-stream micro CNN (R:env/dqn_config.py:92-101, forward :126-133): im2col + MFMA GEMM
+static void conv_explicit_fwd(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    const NetPlan& np = e->np;
+    const int act = cx.act;
+    for (int l = 0; l < cx.NC; l++) {
         const ConvPlan cp = np.conv[l];
         const int M = e->Bl * cp.Ho * cp.Wo;
         Im2colArgs ia;
@@ -1912,82 +1895,72 @@ static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
         fa.N = cp.Co;
         fa.K = cp.K;
         fa.ldc = cp.Co;
-        int np_ = 0;
-        for (int st = 0; st < 3; st++) {
-            if (st == 1 && !dbl) continue;
+        const int nps = for_streams(cx.dbl, [&](int z, int st) {
             float* col = at<float>(e, e->ws_col[l]) + (int64_t)st * M * cp.Kstride;
             if (l == 0) {
-                ia.ring[np_] = st == 0 ? ring_obs : ring_next;
+                ia.ring[z] = st == 0 ? cx.ring_obs : cx.ring_next;
             } else {
-                ia.src[np_] = at<float>(e, e->ws_Hc[l - 1]) + (int64_t)st * e->Bl * cp.Hi * cp.Wi * cp.Ci;
+                ia.src[z] = at<float>(e, e->ws_Hc[l - 1]) + (int64_t)st * e->Bl * cp.Hi * cp.Wi * cp.Ci;
             }
-            ia.col[np_] = col;
-            FwdProblem& p = fa.p[np_++];
-            p.W = (st == 2 ? tparams : params) + cp.off;
+            ia.col[z] = col;
+            FwdProblem& p = fa.p[z];
+            p.W = (st == 2 ? cx.tparams : cx.params) + cp.off;
             p.bias = p.W + (int64_t)cp.Co * cp.K;
             p.C = at<float>(e, e->ws_Hc[l]) + (int64_t)st * M * cp.Co;
             p.A = col;
             p.lda = cp.Kstride;
-        }
-        ia.nstreams = np_;
-        ia.phys = phys;
+        });
+        ia.nstreams = nps;
+        ia.phys = cx.phys;
         ia.ring_stride = e->stride;
         ia.ring_off = np.macro_len;
         ia.Ci = cp.Ci; ia.Hi = cp.Hi; ia.Wi = cp.Wi; ia.Ho = cp.Ho; ia.Wo = cp.Wo;
         ia.kh = cp.kh; ia.kw = cp.kw; ia.sh = cp.sh; ia.sw = cp.sw; ia.ph = cp.ph; ia.pw = cp.pw;
         ia.K = cp.K; ia.Kstride = cp.Kstride; ia.M = M;
-        {
-            KStep k;
-            k.name = "im2col_c" + std::to_string(l + 1);
-            // algorithmic: write the column matrix once, read the source image once
-            k.bytes = 4.0 * nstreams * ((double)M * cp.Kstride + (double)Bl * cp.Ci * cp.Hi * cp.Wi);
-            k.run = [=](hipStream_t s) { return launch_im2col(ia, s); };
-            ks.push_back(k);
-        }
-        KStep k;
-        k.name = "conv_fwd_c" + std::to_string(l + 1);
-        k.flops = 2.0 * nstreams * (double)M * cp.Co * cp.K;
-        k.bytes = 4.0 * (nstreams * (double)M * (cp.Kstride + cp.Co) + 2.0 * cp.Co * (cp.K + 1.0));
+        // algorithmic: write the column matrix once, read the source image once
+        push(ks, "im2col_c" + std::to_string(l + 1),
+             /*flops*/ 0,
+             /*bytes*/ 4.0 * cx.nstreams * ((double)M * cp.Kstride + (double)cx.Bl * cp.Ci * cp.Hi * cp.Wi),
+             [=](hipStream_t s) { return launch_im2col(ia, s); });
+        const std::string name = "conv_fwd_c" + std::to_string(l + 1);
+        const double flops = 2.0 * cx.nstreams * (double)M * cp.Co * cp.K;
+        const double bytes = 4.0 * (cx.nstreams * (double)M * (cp.Kstride + cp.Co) + 2.0 * cp.Co * (cp.K + 1.0));
         const bool vecb = (cp.K % 4) == 0;
-        const int nps = np_;
         // conv GEMMs with enough rows to fill the chip with 128-row tiles (weight slab loaded once per
         // 128 rows): (4,84,84) B=256 convs 1-3 1538/1849/717 -> 408/1228/546 us; (2,27,5) conv 1
         // 31.6 -> 12.8 us, conv 3 (126 tiles) was slower on 128-row tiles and stays on 16 x 64
-        if (fwd_big_mode() && (int64_t)((fa.M + 127) / 128) * np_ >= 256) {
+        if (fwd_big_mode() && (int64_t)((fa.M + 127) / 128) * nps >= 256) {
             fa.ksplit = 1;
-            k.run = [=](hipStream_t s) { return launch_linear_fwd_big(fa, nps, act, vecb, s); };
+            push(ks, name, flops, bytes, [=](hipStream_t s) { return launch_linear_fwd_big(fa, nps, act, vecb, s); });
         } else {
-            k.run = [=](hipStream_t s) { return launch_linear_fwd(fa, nps, act, vecb, s); };
+            push(ks, name, flops, bytes, [=](hipStream_t s) { return launch_linear_fwd(fa, nps, act, vecb, s); });
         }
-        ks.push_back(k);
     }
-    if (NC) {   // 2b. cat(flatten_CHW(conv), macro) (R:env/dqn_config.py:135-138)
-        const ConvPlan cl = np.conv[NC - 1];
-        FlattenArgs fl;
-        memset(&fl, 0, sizeof(fl));
-        int z = 0;
-        for (int st = 0; st < 3; st++) {
-            if (st == 1 && !dbl) continue;
-            fl.Hc[z] = at<float>(e, e->ws_Hc[NC - 1]) + (int64_t)st * e->Bl * cl.Ho * cl.Wo * cl.Co;
-            fl.ring[z] = st == 0 ? ring_obs : ring_next;
-            fl.F[z] = at<float>(e, e->ws_F) + (int64_t)st * e->Bl * np.strideF;
-            z++;
-        }
-        fl.nstreams = z;
-        fl.phys = phys;
-        fl.ring_stride = e->stride;
-        fl.macro_len = np.macro_len;
-        fl.C = cl.Co; fl.Ho = cl.Ho; fl.Wo = cl.Wo;
-        fl.Bl = e->Bl;
-        fl.strideF = np.strideF;
-        KStep k;
-        k.name = "flatten_concat";
-        k.bytes = 4.0 * nstreams * Bl * 2.0 * np.strideF;
-        k.run = [=](hipStream_t s) { return launch_flatten_concat(fl, s); };
-        ks.push_back(k);
-    }
-    }
-    for (int l = 0; l < L; l++) {
+    // 2b. cat(flatten_CHW(conv), macro) (R:env/dqn_config.py:135-138)
+    const ConvPlan cl = np.conv[cx.NC - 1];
+    FlattenArgs fl;
+    memset(&fl, 0, sizeof(fl));
+    fl.nstreams = for_streams(cx.dbl, [&](int z, int st) {
+        fl.Hc[z] = at<float>(e, e->ws_Hc[cx.NC - 1]) + (int64_t)st * e->Bl * cl.Ho * cl.Wo * cl.Co;
+        fl.ring[z] = st == 0 ? cx.ring_obs : cx.ring_next;
+        fl.F[z] = at<float>(e, e->ws_F) + (int64_t)st * e->Bl * np.strideF;
+    });
+    fl.phys = cx.phys;
+    fl.ring_stride = e->stride;
+    fl.macro_len = np.macro_len;
+    fl.C = cl.Co; fl.Ho = cl.Ho; fl.Wo = cl.Wo;
+    fl.Bl = e->Bl;
+    fl.strideF = np.strideF;
+    push(ks, "flatten_concat", 0, 4.0 * cx.nstreams * cx.Bl * 2.0 * np.strideF,
+         [=](hipStream_t s) { return launch_flatten_concat(fl, s); });
+}
+
+// 2c. the dense layers, every stream in one launch per layer
+static void dense_fwd_steps(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    const NetPlan& np = e->np;
+    const int act = cx.act;
+    for (int l = 0; l < cx.L; l++) {
         const LayerPlan lp = np.dense[l];
         FwdArgs fa;
         memset(&fa, 0, sizeof(fa));
@@ -1996,143 +1969,128 @@ static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
         fa.K = lp.in;
         fa.ldc = lp.out;
         float* H = at<float>(e, e->ws_H[l]);
-        int np_ = 0;
-        for (int st = 0; st < 3; st++) {
-            if (st == 1 && !dbl) continue;
-            FwdProblem& p = fa.p[np_++];
+        const int np_ = for_streams(cx.dbl, [&](int z, int st) {
+            FwdProblem& p = fa.p[z];
             const bool tgt = st == 2;
-            p.W = (tgt ? tparams : params) + lp.off;
+            p.W = (tgt ? cx.tparams : cx.params) + lp.off;
             p.bias = p.W + (int64_t)lp.out * lp.in;
             p.C = H + (int64_t)st * e->Bl * lp.out;
-            if (l == 0 && NC) {
+            if (l == 0 && cx.NC) {
                 p.A = at<float>(e, e->ws_F) + (int64_t)st * e->Bl * np.strideF;
                 p.lda = np.strideF;
             } else if (l == 0) {
                 p.A = at<float>(e, e->off[st == 0 ? DQNX_BUF_RING_OBS : DQNX_BUF_RING_NEXT_OBS]);
                 p.lda = e->stride;
-                p.phys = phys;
+                p.phys = cx.phys;
                 p.xcopy = (st == 0) ? at<float>(e, e->ws_xobs) : nullptr;
             } else {
                 const int w = np.dense[l - 1].out;
                 p.A = at<float>(e, e->ws_H[l - 1]) + (int64_t)st * e->Bl * w;
                 p.lda = w;
             }
-        }
-        KStep k;
-        k.name = "linear_fwd_l" + std::to_string(l + 1);
-        k.flops = 2.0 * nstreams * Bl * lp.out * lp.in;
+        });
+        const std::string name = "linear_fwd_l" + std::to_string(l + 1);
+        const double flops = 2.0 * cx.nstreams * cx.Bl * lp.out * lp.in;
         // unique bytes: input rows, weights (online + target), outputs (+ layer-1 row copy)
-        k.bytes = 4.0 * (nstreams * Bl * lp.in + 2.0 * (lp.out * (double)lp.in + lp.out) + nstreams * Bl * lp.out
-                         + (l == 0 && !NC ? Bl * lp.in : 0.0));
+        const double bytes = 4.0 * (cx.nstreams * cx.Bl * lp.in + 2.0 * (lp.out * (double)lp.in + lp.out) + cx.nstreams * cx.Bl * lp.out
+                                    + (l == 0 && !cx.NC ? cx.Bl * lp.in : 0.0));
         const bool vecb = (lp.in % 4) == 0;
         // large-K layers that read dense rows (not the ring gather): 128x128 tiles + split-K into
         // the layer's dW partial slabs (free until the backward), then an ordered reduce
         const uint64_t part_floats = (uint64_t)e->slices[l] * ((uint64_t)lp.out * lp.in + lp.out);
         int kchunk = 0;
         const int ksplit = fwd_big_ksplit(e->Bl, lp.out, lp.in, np_, (int64_t)part_floats, &kchunk);
-        if (l == 0 && NC && e->f1_ksplit) {
+        if (l == 0 && cx.NC && e->f1_ksplit) {
             fa.ksplit = e->f1_ksplit;
             fa.kchunk = e->f1_kchunk;
             fa.partial = at<float>(e, e->ws_fpart);
 #ifdef DQNX_STAMPS
             fa.stamps = at<int64_t>(e, e->ws_stamps);
 #endif
-            k.run = [=](hipStream_t s) { return launch_linear_fwd_split(fa, np_, act, vecb, s); };
-            ks.push_back(k);
+            push(ks, name, flops, bytes, [=](hipStream_t s) { return launch_linear_fwd_split(fa, np_, act, vecb, s); });
             // one slab (F < 256, or more tiles than compute units): the kernel's epilogue already wrote
             // act(sum + bias) into H; a reduce would overwrite it from the slabs it never filled
             if (fa.ksplit == 1) continue;
-            KStep kr;
-            kr.name = k.name + "_reduce";
-            kr.bytes = 4.0 * ((double)fa.ksplit + 1) * np_ * Bl * lp.out;
-            kr.run = [=](hipStream_t s) { return launch_linear_fwd_reduce(fa, np_, act, s); };
-            ks.push_back(kr);
+            push(ks, name + "_reduce", 0, 4.0 * ((double)fa.ksplit + 1) * np_ * cx.Bl * lp.out,
+                 [=](hipStream_t s) { return launch_linear_fwd_reduce(fa, np_, act, s); });
             continue;
         }
         const int big_min_k = tuning_knob("DQNX_FWD_BIG_MINK", 8192);
-        if ((l > 0 || NC) && lp.in >= big_min_k && e->Bl >= 64 && fwd_big_mode() &&
+        if ((l > 0 || cx.NC) && lp.in >= big_min_k && e->Bl >= 64 && fwd_big_mode() &&
             (uint64_t)ksplit * np_ * e->Bl * lp.out <= part_floats) {
             fa.ksplit = ksplit;
             fa.kchunk = kchunk;
             fa.partial = at<float>(e, e->ws_part[l]);
-            k.run = [=](hipStream_t s) { return launch_linear_fwd_big(fa, np_, act, vecb, s); };
-            ks.push_back(k);
+            push(ks, name, flops, bytes, [=](hipStream_t s) { return launch_linear_fwd_big(fa, np_, act, vecb, s); });
             if (ksplit == 1) continue;   // (as above: the one-slab epilogue wrote H)
-            KStep kr;
-            kr.name = k.name + "_reduce";
-            kr.bytes = 4.0 * ((double)ksplit + 1) * np_ * Bl * lp.out;
-            kr.run = [=](hipStream_t s) { return launch_linear_fwd_reduce(fa, np_, act, s); };
-            ks.push_back(kr);
+            push(ks, name + "_reduce", 0, 4.0 * ((double)ksplit + 1) * np_ * cx.Bl * lp.out,
+                 [=](hipStream_t s) { return launch_linear_fwd_reduce(fa, np_, act, s); });
             continue;
         }
-        k.run = [=](hipStream_t s) { return launch_linear_fwd(fa, np_, act, vecb, s); };
-        ks.push_back(k);
+        push(ks, name, flops, bytes, [=](hipStream_t s) { return launch_linear_fwd(fa, np_, act, vecb, s); });
     }
+}
 
-    // 3. head + TD + Huber + head backward (R:dqn/agent.py:209-221, R:dqn/network.py:90-96)
-    {
-        HeadArgs ha;
-        memset(&ha, 0, sizeof(ha));
-        ha.Bl = e->Bl;
-        ha.F = np.F;
-        ha.A = A;
-        ha.NH = np.NH;
-        ha.head_kind = c.net.head;
-        ha.algo = c.algo;
-        ha.head_params = (int)np.head_params;
-        ha.inv_bg = (float)(1.0 / (double)e->Bg);
-        ha.gamma = (float)c.gamma;
-        ha.H = at<float>(e, e->ws_H[L - 1]);
-        ha.Wo = params + np.head_off;
-        ha.Wt = tparams + np.head_off;
-        ha.phys = phys;
-        ha.act = at<int32_t>(e, e->off[DQNX_BUF_RING_ACT]);
-        ha.rew = at<float>(e, e->off[DQNX_BUF_RING_REW]);
-        ha.done = at<float>(e, e->off[DQNX_BUF_RING_DONE]);
-        ha.isw = (c.algo == DQNX_ALGO_PER_DOUBLE) ? at<float>(e, e->off[DQNX_BUF_IS_WEIGHTS]) + e->shard_begin : nullptr;
-        ha.abs_td_out = (c.algo == DQNX_ALGO_PER_DOUBLE) ? at<float>(e, e->off[DQNX_BUF_PER_ABS_TD]) + e->shard_begin
-                                                         : nullptr;
-        ha.Q = at<float>(e, e->off[DQNX_BUF_Q]);
-        ha.td = at<float>(e, e->off[DQNX_BUF_TD]);
-        ha.dZ = at<float>(e, e->ws_dZ[L - 1]);
-        ha.dhead = at<float>(e, e->ws_dhead);
-        if (L >= 2 && e->bwd_plan == 1) {
-            ha.W_last = params + np.dense[L - 1].off;
-            ha.Hprev = at<float>(e, e->ws_H[L - 2]);
-            ha.dZprev = at<float>(e, e->ws_dZ[L - 2]);
-            ha.in_prev = np.dense[L - 1].in;
-        }
-        ha.loss_partial = at<float>(e, e->ws_loss_part);
-        ha.ctrl = ctrl;
-        ha.beta1 = (float)c.beta1;
-        ha.beta2 = (float)c.beta2;
-        ha.lr = (float)c.lr;
-        ha.ab = adam_bias_args(e);
-        ha.stamps = at<int64_t>(e, e->ws_stamps);
-        KStep k;
-        k.name = "head_td_loss";
-        const double F = np.F, NH = np.NH;
-        k.flops = 2.0 * Bl * NH * F * (nstreams + 2.0);
-        k.bytes = 4.0 * (nstreams * Bl * F + 2.0 * np.head_params + Bl * F + e->tiles * (double)np.head_params
-                         + 3.0 * Bl * A + 6.0 * Bl);
-        k.run = [=](hipStream_t s) { return launch_head(ha, act, s); };
-        ks.push_back(k);
+// 3. head + TD + Huber + head backward (R:dqn/agent.py:209-221, R:dqn/network.py:90-96)
+static void head_step(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    const dqnx_config& c = e->cfg;
+    const NetPlan& np = e->np;
+    const int act = cx.act;
+    HeadArgs ha;
+    memset(&ha, 0, sizeof(ha));
+    ha.Bl = e->Bl;
+    ha.F = np.F;
+    ha.A = cx.A;
+    ha.NH = np.NH;
+    ha.head_kind = c.net.head;
+    ha.algo = c.algo;
+    ha.head_params = (int)np.head_params;
+    ha.inv_bg = (float)(1.0 / (double)e->Bg);
+    ha.gamma = (float)c.gamma;
+    ha.H = at<float>(e, e->ws_H[cx.L - 1]);
+    ha.Wo = cx.params + np.head_off;
+    ha.Wt = cx.tparams + np.head_off;
+    ha.phys = cx.phys;
+    ha.act = at<int32_t>(e, e->off[DQNX_BUF_RING_ACT]);
+    ha.rew = at<float>(e, e->off[DQNX_BUF_RING_REW]);
+    ha.done = at<float>(e, e->off[DQNX_BUF_RING_DONE]);
+    ha.isw = (c.algo == DQNX_ALGO_PER_DOUBLE) ? at<float>(e, e->off[DQNX_BUF_IS_WEIGHTS]) + e->shard_begin : nullptr;
+    ha.abs_td_out = (c.algo == DQNX_ALGO_PER_DOUBLE) ? at<float>(e, e->off[DQNX_BUF_PER_ABS_TD]) + e->shard_begin
+                                                     : nullptr;
+    ha.Q = at<float>(e, e->off[DQNX_BUF_Q]);
+    ha.td = at<float>(e, e->off[DQNX_BUF_TD]);
+    ha.dZ = at<float>(e, e->ws_dZ[cx.L - 1]);
+    ha.dhead = at<float>(e, e->ws_dhead);
+    if (cx.L >= 2 && e->bwd_plan == 1) {
+        ha.W_last = cx.params + np.dense[cx.L - 1].off;
+        ha.Hprev = at<float>(e, e->ws_H[cx.L - 2]);
+        ha.dZprev = at<float>(e, e->ws_dZ[cx.L - 2]);
+        ha.in_prev = np.dense[cx.L - 1].in;
     }
+    ha.loss_partial = at<float>(e, e->ws_loss_part);
+    ha.ctrl = cx.ctrl;
+    ha.beta1 = (float)c.beta1;
+    ha.beta2 = (float)c.beta2;
+    ha.lr = (float)c.lr;
+    ha.ab = adam_bias_args(e);
+    ha.stamps = at<int64_t>(e, e->ws_stamps);
+    const double F = np.F, NH = np.NH;
+    push(ks, "head_td_loss",
+         /*flops*/ 2.0 * cx.Bl * NH * F * (cx.nstreams + 2.0),
+         /*bytes*/ 4.0 * (cx.nstreams * cx.Bl * F + 2.0 * np.head_params + cx.Bl * F + e->tiles * (double)np.head_params
+                          + 3.0 * cx.Bl * cx.A + 6.0 * cx.Bl),
+         [=](hipStream_t s) { return launch_head(ha, act, s); });
+}
 
-    // 3b. PER priorities (R:dqn/agent.py:263-265): single GPU here; under DP after the
-    //     all-gather of |delta|, in dqnx_apply_grads
-    if (c.algo == DQNX_ALGO_PER_DOUBLE && !(flags & DQNX_STEP_GRADS_ONLY)) {
-        KStep k;
-        k.name = "per_update";
-        k.bytes = Bg_ * (4.0 + 4.0 + 8.0 * 2.0 * 21.0);
-        k.run = [=](hipStream_t s) { return enqueue_per_update(e, idx, s); };
-        ks.push_back(k);
-    }
-
-    if (e->bwd_plan == 0) {
-    // 4. backward levels L..1: dX of the level below + split-K dW of this level
-    //    (level L also computes the head-weight gradient from the head kernel's dHead)
-    for (int l = L - 1; l >= 0; l--) {
+// 4. backward levels L..1: dX of the level below + split-K dW of this level
+//    (level L also computes the head-weight gradient from the head kernel's dHead)
+static void dense_bwd_steps(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    const dqnx_config& c = e->cfg;
+    const NetPlan& np = e->np;
+    const int act = cx.act;
+    for (int l = cx.L - 1; l >= 0; l--) {
         const LayerPlan lp = np.dense[l];
         BwdArgs ba;
         memset(&ba, 0, sizeof(ba));
@@ -2140,7 +2098,7 @@ static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
         ba.Bl = e->Bl;
         ba.in = lp.in;
         ba.out = lp.out;
-        ba.W = params + lp.off;
+        ba.W = cx.params + lp.off;
         ba.kslice = e->kslice[l];
         ba.dw_slices = e->slices[l];
         DwProblem& d = ba.dw[ba.ndw++];
@@ -2155,7 +2113,7 @@ static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
             ba.dZprev = at<float>(e, e->ws_dZ[l - 1]);
             d.X = ba.Hprev;
             d.ldx = lp.in;
-        } else if (NC) {   // dense input F = cat(conv features, macro): dF, masked by the conv's ELU
+        } else if (cx.NC) {   // dense input F = cat(conv features, macro): dF, masked by the conv's ELU
             ba.Hprev = at<float>(e, e->ws_F);
             ba.ldh = np.strideF;
             ba.dZprev = at<float>(e, e->ws_dF);
@@ -2167,298 +2125,285 @@ static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
         }
         d.partial = at<float>(e, e->ws_part[l]);
         d.pstride = (int64_t)lp.out * lp.in + lp.out;
-        const bool dx = l > 0 || NC;
-        double flops = 2.0 * Bl * lp.out * (lp.in + 1.0) + (dx ? 2.0 * Bl * lp.out * lp.in : 0.0);
-        double bytes = 4.0 * (Bl * lp.out + Bl * lp.in + ba.dw_slices * (lp.out * (lp.in + 1.0))
-                              + (dx ? lp.out * (double)lp.in + 2.0 * Bl * lp.in : 0.0));
+        const bool dx = l > 0 || cx.NC;
+        double flops = 2.0 * cx.Bl * lp.out * (lp.in + 1.0) + (dx ? 2.0 * cx.Bl * lp.out * lp.in : 0.0);
+        double bytes = 4.0 * (cx.Bl * lp.out + cx.Bl * lp.in + ba.dw_slices * (lp.out * (lp.in + 1.0))
+                              + (dx ? lp.out * (double)lp.in + 2.0 * cx.Bl * lp.in : 0.0));
         // very large levels (the (4,84,84) variant's 56,462 -> 512 dense 1): 64 x 64 tiles, a quarter of
         // the 32 x 32 workgroups with four times the MFMAs per operand pass: its backward level 434 ->
         // 351 us; the HEAD net's 1358 -> 512 keeps 32 x 32 (16.1 us; 25.9 with 64 x 64: ~1 workgroup per
         // CU, latency-bound).  DQNX_BWD_TS=32 / 64 forces the edge
         const int bts = route_knob("DQNX_BWD_TS", 0);
         if (bts == 64 || (bts == 0 && (int64_t)(lp.in + 1) * lp.out >= ((int64_t)4 << 20) && e->Bl >= 64)) ba.ts = 64;
-        if (l == L - 1) {   // head weight gradient: dHead^T [H_L | 1]
+        if (l == cx.L - 1) {   // head weight gradient: dHead^T [H_L | 1]
             DwProblem& h = ba.dw[ba.ndw++];
             h.dZ = at<float>(e, e->ws_dhead);
             h.ldz = 16;
-            h.X = at<float>(e, e->ws_H[L - 1]);
+            h.X = at<float>(e, e->ws_H[cx.L - 1]);
             h.ldx = np.F;
             h.in = np.F;
             h.out = np.NH;
             h.partial = at<float>(e, e->ws_head_part);
             h.pstride = head_pstride(np);
             h.head_kind = c.net.head;
-            h.A = A;
-            flops += 2.0 * Bl * np.NH * (np.F + 1.0);
-            bytes += 4.0 * (16.0 * Bl + ba.dw_slices * (double)np.head_params);
+            h.A = cx.A;
+            flops += 2.0 * cx.Bl * np.NH * (np.F + 1.0);
+            bytes += 4.0 * (16.0 * cx.Bl + ba.dw_slices * (double)np.head_params);
         }
         bwd_level_grid(ba);
-        KStep k;
-        k.name = "linear_bwd_l" + std::to_string(l + 1);
-        k.flops = flops;
-        k.bytes = bytes;
-        k.run = [=](hipStream_t s) { return launch_bwd_level(ba, act, s); };
-        ks.push_back(k);
+        push(ks, "linear_bwd_l" + std::to_string(l + 1), flops, bytes,
+             [=](hipStream_t s) { return launch_bwd_level(ba, act, s); });
     }
+}
 
-    // 4b'. implicit-GEMM conv backward, last conv first: dW (+ db) slabs, then the data gradient
-    //      with the previous conv's activation derivative in its epilogue
-    if (NC && e->conv_ig) {
-        for (int l = NC - 1; l >= 0; l--) {
-            const ConvPlan cp = np.conv[l];
-            const bool last = l == NC - 1;
-            const double M = (double)e->Bl * cp.Ho * cp.Wo;
-            // this conv's dZ (NHWC): for the last conv dF (CHW-flatten rows, masked by the dense
-            // layer's dx role) transposed, else what the next conv's data gradient wrote
-            if (last) {
-                UnflattenArgs ua;
-                ua.dF = at<float>(e, e->ws_dF);
-                ua.ldf = np.dense[0].in;
-                ua.dZ = at<float>(e, e->ws_dZc[l]);
-                ua.Bl = e->Bl;
-                ua.C = cp.Co; ua.Ho = cp.Ho; ua.Wo = cp.Wo;
-                KStep k;
-                k.name = "unflatten";
-                k.bytes = 8.0 * M * cp.Co;
-                k.run = [=](hipStream_t s) { return launch_unflatten_tiled(ua, s); };
-                ks.push_back(k);
-            }
-            const float* dZ = at<float>(e, e->ws_dZc[l]);
-            const int64_t dzb = (int64_t)cp.Ho * cp.Wo * cp.Co;
-            const int dzp = cp.Co, dzc = 1;
-            ConvDwIgArgs d;
-            cig_dw_geom(cp, e->Bl, l == 0, d);
-            CigSource& X = d.X;
-            X.H = cp.Hi; X.W = cp.Wi; X.C = cp.Ci;
-            if (l == 0) {
-                X.base[0] = ring_obs;
-                X.phys = phys;
-                X.bstride = e->stride;
-                X.off = np.macro_len;
-                X.pstride = 1;
-                X.cstride = cp.Hi * cp.Wi;
-            } else {
-                X.base[0] = at<float>(e, e->ws_Hc[l - 1]);   // stream 0
-                X.bstride = (int64_t)cp.Hi * cp.Wi * cp.Ci;
-                X.pstride = cp.Ci;
-                X.cstride = 1;
-            }
-            d.dZ = dZ;
-            d.dzb = dzb;
-            d.dzp = dzp;
-            d.dzc = dzc;
-            d.partial = at<float>(e, e->ws_cpart[l]);
-            {
-                KStep k;
-                k.name = "conv_dw_c" + std::to_string(l + 1);
-                k.flops = 2.0 * M * cp.Co * (cp.K + 1.0);
-                k.bytes = 4.0 * (M * cp.Co + Bl * (double)cp.Ci * cp.Hi * cp.Wi + (double)d.slices * d.pstride);
-                k.run = [=](hipStream_t s) { return launch_conv_dw_ig(d, s); };
-                ks.push_back(k);
-            }
-            if (l == 0) continue;
-            const ConvPlan pp = np.conv[l - 1];
-            ConvIgArgs ca;
-            cig_dx_geom(cp, e->Bl, last, ca);
-            ca.act = act;
-            ca.src.base[0] = dZ;
-            ca.src.bstride = dzb;
-            ca.src.pstride = dzp;
-            ca.src.cstride = dzc;
-            ca.W[0] = at<float>(e, e->ws_wpermT[l]);
-            ca.out[0] = at<float>(e, e->ws_dZc[l - 1]);
-            ca.Hprev = at<float>(e, e->ws_Hc[l - 1]);   // stream 0
-            ca.ob = (int64_t)pp.Ho * pp.Wo * pp.Co;
-            ca.orow = pp.Wo * pp.Co;
-            ca.opix = pp.Co;
-            ca.och = 1;
-            KStep k;
-            k.name = "conv_dx_c" + std::to_string(l + 1);
-            k.flops = 2.0 * M * cp.Co * cp.K;
-            k.bytes = 4.0 * (M * cp.Co + 2.0 * Bl * pp.Ho * pp.Wo * pp.Co + (double)cp.Co * cp.K);
-            k.run = [=](hipStream_t s) { return launch_conv_ig(ca, CIG_EPI_DX, s); };
-            ks.push_back(k);
-        }
-    }
-    // 4b''. micro-CNN backward: data gradients of every conv (one launch, stream 0), then every
-    //       conv's weight gradient as split-K slabs (one launch)
-    if (NC && e->micro) {
-        MicroDxArgs xa;
-        memset(&xa, 0, sizeof(xa));
-        for (int l = 0; l < NC; l++) xa.c[l] = mconv[l];
-        xa.nc = NC;
-        xa.Bl = e->Bl;
-        xa.S = e->micro_dx_S;
-        xa.groups = (e->Bl + xa.S - 1) / xa.S;
-        xa.dF = at<float>(e, e->ws_dF);
-        xa.ldf = np.dense[0].in;
-        micro_dx_layout(mconv, NC, xa.S, xa.lds_d, &xa.zero);
-        micro_dx_waves(xa);
-        xa.lds_floats = e->micro_dx_lds;
-#ifdef DQNX_STAMPS
-        xa.stamps = at<int64_t>(e, e->ws_stamps);
-#endif
-        double xf = 0, xb = 0;
-        for (int l = 1; l < NC; l++) {
-            const ConvPlan& cp = np.conv[l];
-            xf += 2.0 * Bl * cp.Ho * cp.Wo * (double)cp.Co * cp.K;
-            xb += 4.0 * (Bl * cp.Ho * cp.Wo * (double)cp.Co + 2.0 * Bl * cp.Hi * cp.Wi * cp.Ci + cp.Co * (double)cp.K);
-        }
-        KStep kx;
-        kx.name = "micro_dx";
-        kx.flops = xf;
-        kx.bytes = xb;
-        kx.run = [=](hipStream_t s) { return launch_micro_dx(xa, s); };
-        ks.push_back(kx);
-        MicroDwArgs da = e->micro_dw;
-        da.ring_obs = ring_obs;
-        da.stamps = at<int64_t>(e, e->ws_stamps);
-        da.err = &ctrl_of(e)->error;
-        da.phys = phys;
-        da.ring_stride = e->stride;
-        da.macro_len = np.macro_len;
-        double wf = 0, wb = 0;
-        for (int l = 0; l < NC; l++) {
-            const ConvPlan& cp = np.conv[l];
-            MicroDwLayer& L = da.L[l];
-            L.D = at<float>(e, e->ws_dZc[l]);
-            L.X = l > 0 ? at<float>(e, e->ws_Hc[l - 1]) : nullptr;
-            L.partial = at<float>(e, e->ws_cpart[l]);
-            wf += 2.0 * Bl * cp.Ho * cp.Wo * (double)cp.Co * (cp.K + 1.0);
-            wb += 4.0 * (Bl * cp.Ho * cp.Wo * (double)cp.Co + Bl * (double)cp.Ci * cp.Hi * cp.Wi + (double)L.slices * L.pstride);
-        }
-        KStep kw;
-        kw.name = "micro_dw";
-        kw.flops = wf;
-        kw.bytes = wb;
-        kw.run = [=](hipStream_t s) { return launch_micro_dw(da, s); };
-        ks.push_back(kw);
-    }
-    // 4b. micro CNN backward: unflatten dF, then per conv (last first) dW + dX columns, col2im
-    if (NC && !e->conv_ig && !e->micro) {
-        {
-            const ConvPlan cl = np.conv[NC - 1];
+// 4b'. implicit-GEMM conv backward, last conv first: dW (+ db) slabs, then the data gradient
+//      with the previous conv's activation derivative in its epilogue
+static void conv_ig_bwd(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    const NetPlan& np = e->np;
+    const int act = cx.act;
+    for (int l = cx.NC - 1; l >= 0; l--) {
+        const ConvPlan cp = np.conv[l];
+        const bool last = l == cx.NC - 1;
+        const double M = (double)e->Bl * cp.Ho * cp.Wo;
+        // this conv's dZ (NHWC): for the last conv dF (CHW-flatten rows, masked by the dense
+        // layer's dx role) transposed, else what the next conv's data gradient wrote
+        if (last) {
             UnflattenArgs ua;
             ua.dF = at<float>(e, e->ws_dF);
             ua.ldf = np.dense[0].in;
-            ua.dZ = at<float>(e, e->ws_dZc[NC - 1]);
+            ua.dZ = at<float>(e, e->ws_dZc[l]);
             ua.Bl = e->Bl;
-            ua.C = cl.Co; ua.Ho = cl.Ho; ua.Wo = cl.Wo;
-            KStep k;
-            k.name = "unflatten";
-            k.bytes = 8.0 * Bl * cl.Co * cl.Ho * cl.Wo;
-            k.run = [=](hipStream_t s) { return launch_unflatten(ua, s); };
-            ks.push_back(k);
+            ua.C = cp.Co; ua.Ho = cp.Ho; ua.Wo = cp.Wo;
+            push(ks, "unflatten", 0, 8.0 * M * cp.Co,
+                 [=](hipStream_t s) { return launch_unflatten_tiled(ua, s); });
         }
-        for (int l = NC - 1; l >= 0; l--) {
-            const ConvPlan cp = np.conv[l];
-            const int M = e->Bl * cp.Ho * cp.Wo;
-            BwdArgs ba;
-            memset(&ba, 0, sizeof(ba));
-            ba.dZ = at<float>(e, e->ws_dZc[l]);
-            ba.Bl = M;
-            ba.in = cp.K;
-            ba.out = cp.Co;
-            ba.W = params + cp.off;
-            ba.kslice = e->ckslice[l];
-            ba.dw_slices = e->cslices[l];
-            // dCol = dZ W (no mask here: col2im applies the previous conv's ELU'); on 128x64 tiles in
-            // its own launch when that fills the chip, else as the dx role of the level
-            const bool dx_big = l > 0 && fwd_big_mode() && conv_dx_big_tiles(M, cp.K) >= 256;
-            BwdArgs bdx;
-            if (l > 0) {
-                ba.Hprev = nullptr;
-                ba.dZprev = at<float>(e, e->ws_dcol);
-                bdx = ba;
-                if (dx_big) ba.dZprev = nullptr;
+        const float* dZ = at<float>(e, e->ws_dZc[l]);
+        const int64_t dzb = (int64_t)cp.Ho * cp.Wo * cp.Co;
+        const int dzp = cp.Co, dzc = 1;
+        ConvDwIgArgs d;
+        cig_dw_geom(cp, e->Bl, l == 0, d);
+        CigSource& X = d.X;
+        X.H = cp.Hi; X.W = cp.Wi; X.C = cp.Ci;
+        if (l == 0) {
+            X.base[0] = cx.ring_obs;
+            X.phys = cx.phys;
+            X.bstride = e->stride;
+            X.off = np.macro_len;
+            X.pstride = 1;
+            X.cstride = cp.Hi * cp.Wi;
+        } else {
+            X.base[0] = at<float>(e, e->ws_Hc[l - 1]);   // stream 0
+            X.bstride = (int64_t)cp.Hi * cp.Wi * cp.Ci;
+            X.pstride = cp.Ci;
+            X.cstride = 1;
+        }
+        d.dZ = dZ;
+        d.dzb = dzb;
+        d.dzp = dzp;
+        d.dzc = dzc;
+        d.partial = at<float>(e, e->ws_cpart[l]);
+        push(ks, "conv_dw_c" + std::to_string(l + 1),
+             /*flops*/ 2.0 * M * cp.Co * (cp.K + 1.0),
+             /*bytes*/ 4.0 * (M * cp.Co + cx.Bl * (double)cp.Ci * cp.Hi * cp.Wi + (double)d.slices * d.pstride),
+             [=](hipStream_t s) { return launch_conv_dw_ig(d, s); });
+        if (l == 0) continue;
+        const ConvPlan pp = np.conv[l - 1];
+        ConvIgArgs ca;
+        cig_dx_geom(cp, e->Bl, last, ca);
+        ca.act = act;
+        ca.src.base[0] = dZ;
+        ca.src.bstride = dzb;
+        ca.src.pstride = dzp;
+        ca.src.cstride = dzc;
+        ca.W[0] = at<float>(e, e->ws_wpermT[l]);
+        ca.out[0] = at<float>(e, e->ws_dZc[l - 1]);
+        ca.Hprev = at<float>(e, e->ws_Hc[l - 1]);   // stream 0
+        ca.ob = (int64_t)pp.Ho * pp.Wo * pp.Co;
+        ca.orow = pp.Wo * pp.Co;
+        ca.opix = pp.Co;
+        ca.och = 1;
+        push(ks, "conv_dx_c" + std::to_string(l + 1),
+             /*flops*/ 2.0 * M * cp.Co * cp.K,
+             /*bytes*/ 4.0 * (M * cp.Co + 2.0 * cx.Bl * pp.Ho * pp.Wo * pp.Co + (double)cp.Co * cp.K),
+             [=](hipStream_t s) { return launch_conv_ig(ca, CIG_EPI_DX, s); });
+    }
+}
+
+// 4b''. micro-CNN backward: data gradients of every conv (one launch, stream 0), then every
+//       conv's weight gradient as split-K slabs (one launch)
+static void conv_micro_bwd(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    const NetPlan& np = e->np;
+    MicroConv mconv[MICRO_MAX_CONV];
+    micro_convs(e, mconv);
+    MicroDxArgs xa;
+    memset(&xa, 0, sizeof(xa));
+    for (int l = 0; l < cx.NC; l++) xa.c[l] = mconv[l];
+    xa.nc = cx.NC;
+    xa.Bl = e->Bl;
+    xa.S = e->micro_dx_S;
+    xa.groups = (e->Bl + xa.S - 1) / xa.S;
+    xa.dF = at<float>(e, e->ws_dF);
+    xa.ldf = np.dense[0].in;
+    micro_dx_layout(mconv, cx.NC, xa.S, xa.lds_d, &xa.zero);
+    micro_dx_waves(xa);
+    xa.lds_floats = e->micro_dx_lds;
+#ifdef DQNX_STAMPS
+    xa.stamps = at<int64_t>(e, e->ws_stamps);
+#endif
+    double xf = 0, xb = 0;
+    for (int l = 1; l < cx.NC; l++) {
+        const ConvPlan& cp = np.conv[l];
+        xf += 2.0 * cx.Bl * cp.Ho * cp.Wo * (double)cp.Co * cp.K;
+        xb += 4.0 * (cx.Bl * cp.Ho * cp.Wo * (double)cp.Co + 2.0 * cx.Bl * cp.Hi * cp.Wi * cp.Ci + cp.Co * (double)cp.K);
+    }
+    push(ks, "micro_dx", xf, xb,
+         [=](hipStream_t s) { return launch_micro_dx(xa, s); });
+    MicroDwArgs da = e->micro_dw;
+    da.ring_obs = cx.ring_obs;
+    da.stamps = at<int64_t>(e, e->ws_stamps);
+    da.err = &ctrl_of(e)->error;
+    da.phys = cx.phys;
+    da.ring_stride = e->stride;
+    da.macro_len = np.macro_len;
+    double wf = 0, wb = 0;
+    for (int l = 0; l < cx.NC; l++) {
+        const ConvPlan& cp = np.conv[l];
+        MicroDwLayer& ml = da.L[l];
+        ml.D = at<float>(e, e->ws_dZc[l]);
+        ml.X = l > 0 ? at<float>(e, e->ws_Hc[l - 1]) : nullptr;
+        ml.partial = at<float>(e, e->ws_cpart[l]);
+        wf += 2.0 * cx.Bl * cp.Ho * cp.Wo * (double)cp.Co * (cp.K + 1.0);
+        wb += 4.0 * (cx.Bl * cp.Ho * cp.Wo * (double)cp.Co + cx.Bl * (double)cp.Ci * cp.Hi * cp.Wi + (double)ml.slices * ml.pstride);
+    }
+    push(ks, "micro_dw", wf, wb,
+         [=](hipStream_t s) { return launch_micro_dw(da, s); });
+}
+
+// 4b. micro CNN backward: unflatten dF, then per conv (last first) dW + dX columns, col2im
+static void conv_explicit_bwd(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    const NetPlan& np = e->np;
+    const int act = cx.act;
+    {
+        const ConvPlan cl = np.conv[cx.NC - 1];
+        UnflattenArgs ua;
+        ua.dF = at<float>(e, e->ws_dF);
+        ua.ldf = np.dense[0].in;
+        ua.dZ = at<float>(e, e->ws_dZc[cx.NC - 1]);
+        ua.Bl = e->Bl;
+        ua.C = cl.Co; ua.Ho = cl.Ho; ua.Wo = cl.Wo;
+        push(ks, "unflatten", 0, 8.0 * cx.Bl * cl.Co * cl.Ho * cl.Wo,
+             [=](hipStream_t s) { return launch_unflatten(ua, s); });
+    }
+    for (int l = cx.NC - 1; l >= 0; l--) {
+        const ConvPlan cp = np.conv[l];
+        const int M = e->Bl * cp.Ho * cp.Wo;
+        BwdArgs ba;
+        memset(&ba, 0, sizeof(ba));
+        ba.dZ = at<float>(e, e->ws_dZc[l]);
+        ba.Bl = M;
+        ba.in = cp.K;
+        ba.out = cp.Co;
+        ba.W = cx.params + cp.off;
+        ba.kslice = e->ckslice[l];
+        ba.dw_slices = e->cslices[l];
+        // dCol = dZ W (no mask here: col2im applies the previous conv's ELU'); on 128x64 tiles in
+        // its own launch when that fills the chip, else as the dx role of the level
+        const bool dx_big = l > 0 && fwd_big_mode() && conv_dx_big_tiles(M, cp.K) >= 256;
+        BwdArgs bdx;
+        if (l > 0) {
+            ba.Hprev = nullptr;
+            ba.dZprev = at<float>(e, e->ws_dcol);
+            bdx = ba;
+            if (dx_big) ba.dZprev = nullptr;
+        }
+        DwProblem& d = ba.dw[ba.ndw++];
+        d.dZ = ba.dZ;
+        d.ldz = cp.Co;
+        d.X = at<float>(e, e->ws_col[l]);   // stream 0 columns
+        d.ldx = cp.Kstride;
+        d.in = cp.K;
+        d.out = cp.Co;
+        d.partial = at<float>(e, e->ws_cpart[l]);
+        d.pstride = (int64_t)cp.Co * cp.K + cp.Co;
+        d.head_kind = -1;
+        bwd_level_grid(ba);
+        const bool dw_big = conv_dw_big(M, cp.K);
+        // the conv_bwd launch: the dW GEMM, with the dx role unless that runs in a launch of its own
+        const bool with_dx = l > 0 && !dx_big && !dw_big;
+        const std::string name = "conv_bwd_c" + std::to_string(l + 1);
+        const double flops = 2.0 * M * cp.Co * (cp.K + 1.0) + (with_dx ? 2.0 * M * cp.Co * (double)cp.K : 0.0);
+        const double bytes = 4.0 * ((double)M * (cp.Co + cp.Kstride) + ba.dw_slices * (double)d.pstride
+                                    + (with_dx ? (double)M * cp.K + cp.Co * (double)cp.K : 0.0));
+        if (dw_big) {   // dx role (if any) runs as conv_dx_c* or stays in a level launch
+            BwdArgs bw = ba;
+            if (ba.dZprev) {    // small dx: keep it in its own level launch without the dW role
+                BwdArgs bl = ba;
+                bl.ndw = 0;
+                bwd_level_grid(bl);
+                push(ks, "conv_dxs_c" + std::to_string(l + 1),
+                     /*flops*/ 2.0 * M * cp.Co * (double)cp.K,
+                     /*bytes*/ 4.0 * ((double)M * cp.K + (double)M * cp.Co + cp.Co * (double)cp.K),
+                     [=](hipStream_t s) { return launch_bwd_level(bl, act, s); });
             }
-            DwProblem& d = ba.dw[ba.ndw++];
-            d.dZ = ba.dZ;
-            d.ldz = cp.Co;
-            d.X = at<float>(e, e->ws_col[l]);   // stream 0 columns
-            d.ldx = cp.Kstride;
-            d.in = cp.K;
-            d.out = cp.Co;
-            d.partial = at<float>(e, e->ws_cpart[l]);
-            d.pstride = (int64_t)cp.Co * cp.K + cp.Co;
-            d.head_kind = -1;
-            bwd_level_grid(ba);
-            KStep k;
-            k.name = "conv_bwd_c" + std::to_string(l + 1);
-            k.flops = 2.0 * M * cp.Co * (cp.K + 1.0) + (l > 0 ? 2.0 * M * cp.Co * (double)cp.K : 0.0);
-            k.bytes = 4.0 * ((double)M * (cp.Co + cp.Kstride) + ba.dw_slices * (double)d.pstride
-                             + (l > 0 ? (double)M * cp.K + cp.Co * (double)cp.K : 0.0));
-            const bool dw_big = conv_dw_big(M, cp.K);
-            if (dw_big) {   // dx role (if any) runs as conv_dx_c* or stays in a level launch
-                BwdArgs bw = ba;
-                if (ba.dZprev) {    // small dx: keep it in its own level launch without the dW role
-                    BwdArgs bl = ba;
-                    bl.ndw = 0;
-                    bwd_level_grid(bl);
-                    KStep kl;
-                    kl.name = "conv_dxs_c" + std::to_string(l + 1);
-                    kl.flops = 2.0 * M * cp.Co * (double)cp.K;
-                    kl.bytes = 4.0 * ((double)M * cp.K + (double)M * cp.Co + cp.Co * (double)cp.K);
-                    kl.run = [=](hipStream_t s) { return launch_bwd_level(bl, act, s); };
-                    ks.push_back(kl);
-                }
-                k.run = [=](hipStream_t s) { return launch_conv_dw_big(bw, s); };
-            } else {
-                k.run = [=](hipStream_t s) { return launch_bwd_level(ba, act, s); };
-            }
-            if (dx_big || dw_big) {   // the conv_bwd launch is the dW GEMM alone
-                k.flops = 2.0 * M * cp.Co * (cp.K + 1.0);
-                k.bytes = 4.0 * ((double)M * (cp.Co + cp.Kstride) + ba.dw_slices * (double)d.pstride);
-            }
-            ks.push_back(k);
-            if (dx_big) {
-                KStep kx;
-                kx.name = "conv_dx_c" + std::to_string(l + 1);
-                kx.flops = 2.0 * M * cp.Co * (double)cp.K;
-                kx.bytes = 4.0 * ((double)M * cp.K + (double)M * cp.Co + cp.Co * (double)cp.K);
-                kx.run = [=](hipStream_t s) { return launch_conv_dx_big(bdx, s); };
-                ks.push_back(kx);
-            }
-            if (l > 0) {
-                const ConvPlan pp = np.conv[l - 1];
-                Col2imArgs ca;
-                ca.dcol = at<float>(e, e->ws_dcol);
-                ca.ldcol = cp.K;
-                ca.Hprev = at<float>(e, e->ws_Hc[l - 1]);      // stream 0
-                ca.dZprev = at<float>(e, e->ws_dZc[l - 1]);
-                ca.Bl = e->Bl;
-                ca.Ci = cp.Ci; ca.Hi = cp.Hi; ca.Wi = cp.Wi; ca.Ho = cp.Ho; ca.Wo = cp.Wo;
-                ca.kh = cp.kh; ca.kw = cp.kw; ca.sh = cp.sh; ca.sw = cp.sw; ca.ph = cp.ph; ca.pw = cp.pw;
-                KStep k2;
-                k2.name = "col2im_c" + std::to_string(l + 1);
-                k2.bytes = 4.0 * ((double)M * cp.K + 2.0 * Bl * pp.Ho * pp.Wo * pp.Co);
-                k2.run = [=](hipStream_t s) { return launch_col2im(ca, act, s); };
-                ks.push_back(k2);
-            }
+            push(ks, name, flops, bytes, [=](hipStream_t s) { return launch_conv_dw_big(bw, s); });
+        } else {
+            push(ks, name, flops, bytes, [=](hipStream_t s) { return launch_bwd_level(ba, act, s); });
+        }
+        if (dx_big) {
+            push(ks, "conv_dx_c" + std::to_string(l + 1),
+                 /*flops*/ 2.0 * M * cp.Co * (double)cp.K,
+                 /*bytes*/ 4.0 * ((double)M * cp.K + (double)M * cp.Co + cp.Co * (double)cp.K),
+                 [=](hipStream_t s) { return launch_conv_dx_big(bdx, s); });
+        }
+        if (l > 0) {
+            const ConvPlan pp = np.conv[l - 1];
+            Col2imArgs ca;
+            ca.dcol = at<float>(e, e->ws_dcol);
+            ca.ldcol = cp.K;
+            ca.Hprev = at<float>(e, e->ws_Hc[l - 1]);      // stream 0
+            ca.dZprev = at<float>(e, e->ws_dZc[l - 1]);
+            ca.Bl = e->Bl;
+            ca.Ci = cp.Ci; ca.Hi = cp.Hi; ca.Wi = cp.Wi; ca.Ho = cp.Ho; ca.Wo = cp.Wo;
+            ca.kh = cp.kh; ca.kw = cp.kw; ca.sh = cp.sh; ca.sw = cp.sw; ca.ph = cp.ph; ca.pw = cp.pw;
+            push(ks, "col2im_c" + std::to_string(l + 1),
+                 /*flops*/ 0,
+                 /*bytes*/ 4.0 * ((double)M * cp.K + 2.0 * cx.Bl * pp.Ho * pp.Wo * pp.Co),
+                 [=](hipStream_t s) { return launch_col2im(ca, act, s); });
         }
     }
+}
 
-    // 5. gradient reduction + Adam (+ soft update); with the in-launch prefetch its extra workgroup
-    //    copies the staged minibatch over the compute slot (every reader of slot 0 ran before)
-    if (key & KEY_SAMPLE_NEXT) {
+// 5. gradient reduction + Adam (+ soft update); with the in-launch prefetch its extra workgroup
+//    copies the staged minibatch over the compute slot (every reader of slot 0 ran before)
+static void adam_tail_step(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    if (cx.key & KEY_SAMPLE_NEXT) {
         AdamArgs aa;
-        KStep k = adam_kstep(e, flags, &aa);
+        KStep k = adam_kstep(e, cx.flags, &aa);
         aa.pf_idx_src = at<int32_t>(e, e->off[DQNX_BUF_BATCH_IDX]) + (size_t)e->Bg;
-        aa.pf_idx_dst = idx;
+        aa.pf_idx_dst = cx.idx;
         aa.pf_nidx = e->Bg;
         aa.pf_phys_src = at<int32_t>(e, e->ws_phys) + (size_t)e->Bl;
-        aa.pf_phys_dst = phys;
+        aa.pf_phys_dst = cx.phys;
         aa.pf_nphys = e->Bl;
         aa.mtc = nullptr;   // the forward's sampler body draws from the MT state itself
         aa.mtc_blocks = 0;
         k.run = adam_run(e, aa);
         ks.push_back(k);
     } else {
-        ks.push_back(adam_kstep(e, flags));
+        ks.push_back(adam_kstep(e, cx.flags));
     }
-    } else {
-    // 4. dZ of levels below L-1 (deeper MLPs only; the head kernel produced dZ_L and dZ_{L-1})
-    for (int l = L - 2; l >= 1; l--) {
+}
+
+// 4. dZ of levels below L-1 (deeper MLPs only; the head kernel produced dZ_L and dZ_{L-1})
+static void dx_chain_steps(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    const NetPlan& np = e->np;
+    const int act = cx.act;
+    for (int l = cx.L - 2; l >= 1; l--) {
         const LayerPlan lp = np.dense[l];
         BwdArgs ba;
         memset(&ba, 0, sizeof(ba));
@@ -2466,7 +2411,7 @@ static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
         ba.Bl = e->Bl;
         ba.in = lp.in;
         ba.out = lp.out;
-        ba.W = params + lp.off;
+        ba.W = cx.params + lp.off;
         ba.Hprev = at<float>(e, e->ws_H[l - 1]);
         ba.ldh = lp.in;
         ba.dZprev = at<float>(e, e->ws_dZ[l - 1]);
@@ -2474,88 +2419,113 @@ static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
         ba.dw_slices = 1;
         ba.kslice = e->Bl;
         bwd_level_grid(ba);
-        KStep k;
-        k.name = "linear_dx_l" + std::to_string(l + 1);
-        k.flops = 2.0 * Bl * lp.out * lp.in;
-        k.bytes = 4.0 * (Bl * lp.out + lp.out * (double)lp.in + 2.0 * Bl * lp.in);
-        k.run = [=](hipStream_t s) { return launch_bwd_level(ba, act, s); };
-        ks.push_back(k);
+        push(ks, "linear_dx_l" + std::to_string(l + 1),
+             /*flops*/ 2.0 * cx.Bl * lp.out * lp.in,
+             /*bytes*/ 4.0 * (cx.Bl * lp.out + lp.out * (double)lp.in + 2.0 * cx.Bl * lp.in),
+             [=](hipStream_t s) { return launch_bwd_level(ba, act, s); });
     }
+}
 
-    // 5. all weight gradients (full minibatch per tile) + Adam (+ soft update) in one launch
+// 5. all weight gradients (full minibatch per tile) + Adam (+ soft update) in one launch
+static void dw_adam_step(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    const dqnx_config& c = e->cfg;
+    const NetPlan& np = e->np;
+    DwAdamArgs da;
+    memset(&da, 0, sizeof(da));
+    double flops = 0, bytes = 0;
+    for (int l = 0; l < cx.L; l++) {
+        const LayerPlan lp = np.dense[l];
+        DwAdamProblem& d = da.pr[da.npr++];
+        d.dZ = at<float>(e, e->ws_dZ[l]);
+        d.ldz = lp.out;
+        if (l > 0) {
+            d.X = at<float>(e, e->ws_H[l - 1]);   // stream 0 rows
+            d.ldx = lp.in;
+        } else {
+            d.X = at<float>(e, e->ws_xobs);
+            d.ldx = e->stride;
+        }
+        d.in = lp.in;
+        d.out = lp.out;
+        d.poff = lp.off;
+        d.head_kind = -1;
+        flops += 2.0 * cx.Bl * lp.out * (lp.in + 1.0);
+        bytes += 4.0 * cx.Bl * (lp.out + lp.in);
+    }
     {
-        DwAdamArgs da;
-        memset(&da, 0, sizeof(da));
-        double flops = 0, bytes = 0;
-        for (int l = 0; l < L; l++) {
-            const LayerPlan lp = np.dense[l];
-            DwAdamProblem& d = da.pr[da.npr++];
-            d.dZ = at<float>(e, e->ws_dZ[l]);
-            d.ldz = lp.out;
-            if (l > 0) {
-                d.X = at<float>(e, e->ws_H[l - 1]);   // stream 0 rows
-                d.ldx = lp.in;
-            } else {
-                d.X = at<float>(e, e->ws_xobs);
-                d.ldx = e->stride;
-            }
-            d.in = lp.in;
-            d.out = lp.out;
-            d.poff = lp.off;
-            d.head_kind = -1;
-            flops += 2.0 * Bl * lp.out * (lp.in + 1.0);
-            bytes += 4.0 * Bl * (lp.out + lp.in);
-        }
-        {
-            DwAdamProblem& d = da.pr[da.npr++];
-            d.dZ = at<float>(e, e->ws_dhead);
-            d.ldz = 16;
-            d.X = at<float>(e, e->ws_H[L - 1]);
-            d.ldx = np.F;
-            d.in = np.F;
-            d.out = np.NH;
-            d.poff = np.head_off;
-            d.head_kind = c.net.head;
-            d.A = A;
-            flops += 2.0 * Bl * np.NH * (np.F + 1.0);
-            bytes += 4.0 * Bl * (16.0 + np.F);
-        }
-        dw_adam_grid(da);
-        da.Bl = e->Bl;
-        da.mode = (flags & DQNX_STEP_GRADS_ONLY) ? 0 : 1;
-        da.soft = (flags & DQNX_STEP_SOFT_UPDATE) ? 1 : 0;
-        da.n_params = np.P;
-        da.p = params;
-        da.m = at<float>(e, e->off[DQNX_BUF_ADAM_M]);
-        da.v = at<float>(e, e->off[DQNX_BUF_ADAM_V]);
-        da.grads = at<float>(e, e->off[DQNX_BUF_GRADS]);
-        da.target = tparams;
-        da.ctrl = ctrl;
-        da.w1 = (float)(1.0 - c.beta1);          // Python: exp_avg.lerp_(grad, 1 - beta1)
-        da.beta2 = (float)c.beta2;
-        da.c2 = (float)(1.0 - c.beta2);
-        da.eps = (float)c.adam_eps;
-        da.tau = (float)(c.tau * c.n_env);
-        da.one_minus_tau = (float)(1.0 - c.tau * c.n_env);
-        da.adam_table = at<float>(e, e->ws_adam_tab);
-        da.adam_table_len = kAdamTable;
-        da.beta1d = c.beta1;
-        da.beta2d = c.beta2;
-        da.lrd = c.lr;
-        da.loss_partial = at<float>(e, e->ws_loss_part);
-        da.n_loss_partial = e->tiles;
-        da.batch_global = e->Bg;
-        const double P = (double)np.P;
-        bytes += 4.0 * (P + (da.mode ? 6.0 * P + (da.soft ? 2.0 * P : 0.0) : 0.0));
-        flops += da.mode ? 12.0 * P : 0.0;
-        KStep k;
-        k.name = da.mode ? "dw_adam" : "dw_grads";
-        k.flops = flops;
-        k.bytes = bytes;
-        k.run = [=](hipStream_t s) { return launch_dw_adam(da, s); };
-        ks.push_back(k);
+        DwAdamProblem& d = da.pr[da.npr++];
+        d.dZ = at<float>(e, e->ws_dhead);
+        d.ldz = 16;
+        d.X = at<float>(e, e->ws_H[cx.L - 1]);
+        d.ldx = np.F;
+        d.in = np.F;
+        d.out = np.NH;
+        d.poff = np.head_off;
+        d.head_kind = c.net.head;
+        d.A = cx.A;
+        flops += 2.0 * cx.Bl * np.NH * (np.F + 1.0);
+        bytes += 4.0 * cx.Bl * (16.0 + np.F);
     }
+    dw_adam_grid(da);
+    da.Bl = e->Bl;
+    da.mode = (cx.flags & DQNX_STEP_GRADS_ONLY) ? 0 : 1;
+    da.soft = (cx.flags & DQNX_STEP_SOFT_UPDATE) ? 1 : 0;
+    da.n_params = np.P;
+    da.p = cx.params;
+    da.m = at<float>(e, e->off[DQNX_BUF_ADAM_M]);
+    da.v = at<float>(e, e->off[DQNX_BUF_ADAM_V]);
+    da.grads = at<float>(e, e->off[DQNX_BUF_GRADS]);
+    da.target = cx.tparams;
+    da.ctrl = cx.ctrl;
+    da.w1 = (float)(1.0 - c.beta1);          // Python: exp_avg.lerp_(grad, 1 - beta1)
+    da.beta2 = (float)c.beta2;
+    da.c2 = (float)(1.0 - c.beta2);
+    da.eps = (float)c.adam_eps;
+    da.tau = (float)(c.tau * c.n_env);
+    da.one_minus_tau = (float)(1.0 - c.tau * c.n_env);
+    da.adam_table = at<float>(e, e->ws_adam_tab);
+    da.adam_table_len = kAdamTable;
+    da.beta1d = c.beta1;
+    da.beta2d = c.beta2;
+    da.lrd = c.lr;
+    da.loss_partial = at<float>(e, e->ws_loss_part);
+    da.n_loss_partial = e->tiles;
+    da.batch_global = e->Bg;
+    const double P = (double)np.P;
+    bytes += 4.0 * (P + (da.mode ? 6.0 * P + (da.soft ? 2.0 * P : 0.0) : 0.0));
+    flops += da.mode ? 12.0 * P : 0.0;
+    push(ks, da.mode ? "dw_adam" : "dw_grads", flops, bytes,
+         [=](hipStream_t s) { return launch_dw_adam(da, s); });
+}
+
+// The compute launches of a plan key: the sampler, then the launches of the engine's plan and conv route,
+// picked once.
+static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
+    const StepCtx cx = step_ctx(e, key);
+    std::vector<KStep> ks;
+    sample_steps(cx, ks);
+    if (e->bwd_plan == 2) {
+        fused_steps(cx, ks);
+        return ks;
     }
+    // 2. forward layers: streams 0 online(obs), 1 online(next) [double], 2 target(next)
+    if (cx.NC && e->conv_ig) conv_ig_fwd(cx, ks);
+    else if (cx.NC && e->micro) conv_micro_fwd(cx, ks);
+    else if (cx.NC) conv_explicit_fwd(cx, ks);
+    dense_fwd_steps(cx, ks);
+    head_step(cx, ks);
+    if (e->cfg.algo == DQNX_ALGO_PER_DOUBLE && !(cx.flags & DQNX_STEP_GRADS_ONLY)) per_update_step(cx, ks);
+    if (e->bwd_plan != 0) {   // plan 1: the head kernel produced dZ_L and dZ_{L-1}
+        dx_chain_steps(cx, ks);
+        dw_adam_step(cx, ks);
+        return ks;
+    }
+    dense_bwd_steps(cx, ks);
+    if (cx.NC && e->conv_ig) conv_ig_bwd(cx, ks);
+    else if (cx.NC && e->micro) conv_micro_bwd(cx, ks);
+    else if (cx.NC) conv_explicit_bwd(cx, ks);
+    adam_tail_step(cx, ks);
     return ks;
 }
 
@@ -2656,8 +2626,8 @@ static DwAdam16Args dw16_subset(const DwAdam16Args& a, uint32_t mask, bool first
 // flags & KEY_CLIP: the Adam launch multiplies every gradient element by the step's clip coefficient.
 // parts: 1 = the PER priority update's own launches, 2 = the Adam launch (a clipped step's plan lists
 // them as launches of their own)
-int enqueue_apply(dqnx_engine* e, int flags, hipStream_t s, int parts) {
-    const bool keep_blk = (flags & 0x200) != 0;   // (a prefetched minibatch is pending: no sampler launch next)
+int enqueue_apply(dqnx_engine* e, int flags, hipStream_t s, int parts = 3) {
+    const bool keep_blk = (flags & KEY_KEEP_BLK) != 0;   // (a prefetched minibatch is pending: no sampler launch next)
     const dqnx_config& c = e->cfg;
     const float* gscale = (flags & KEY_CLIP) ? at<float>(e, e->off[DQNX_BUF_GRAD_CLIP] + kClipCoefOff) : nullptr;
     // priorities from the all-gathered |delta| (DP); k_per_prop's workgroups ride in the Adam launch
@@ -2722,7 +2692,7 @@ int enqueue_apply(dqnx_engine* e, int flags, hipStream_t s, int parts) {
             da.pprop = pua;
             da.pprop_wgs = (e->Bg + 511) / 512;
         }
-        if (e->mtc_blocks > 0 && !prop_in_adam && (flags & 0x400)) {   // the next step's in-forward draw reads its MT blocks from the cache
+        if (e->mtc_blocks > 0 && !prop_in_adam && (flags & KEY_KEEP_MTC)) {   // the next step's in-forward draw reads its MT blocks from the cache
             da.mtc = at<uint32_t>(e, e->ws_mtc);
             da.mtc_blocks = e->mtc_blocks;
         }
@@ -2734,6 +2704,71 @@ int enqueue_apply(dqnx_engine* e, int flags, hipStream_t s, int parts) {
         aa.pprop_wgs = (e->Bg + 255) / 256;
     }
     return launch_adam(aa, s);
+}
+
+// The tail of a clipped step (KEY_CLIP_TAIL), and all of a clipped dqnx_apply_grads: the gradient's sum
+// of squares, the coefficient, then dqnx_apply_grads' launches reading it (clip.hip).
+static std::vector<KStep> clip_tail_steps(dqnx_engine* e, int key) {
+    std::vector<KStep> ks;
+    const double P = (double)e->np.P;
+    const ClipArgs ca = clip_args(e);
+    const int akey = (key & (DQNX_STEP_SOFT_UPDATE | KEY_KEEP_BLK | KEY_KEEP_MTC)) | KEY_CLIP;
+    const bool soft = (key & DQNX_STEP_SOFT_UPDATE) != 0;
+    KStep k;
+    k.name = "grad_sumsq";
+    k.flops = 2.0 * P;
+    k.bytes = 4.0 * P + 8.0 * ca.n_part;
+    k.run = [=](hipStream_t s) { return launch_grad_sumsq(ca, s); };
+    ks.push_back(k);
+    k.name = "clip_coef";
+    k.flops = 0;
+    k.bytes = 8.0 * ca.n_part + sizeof(dqnx_grad_clip_info);
+    k.run = [=](hipStream_t s) { return launch_clip_coef(ca, s); };
+    ks.push_back(k);
+    if (e->cfg.algo == DQNX_ALGO_PER_DOUBLE) {   // the tree update dqnx_apply_grads makes
+        k.name = "per_update";
+        k.flops = 0;
+        k.bytes = 12.0 * e->Bg;
+        k.run = [=](hipStream_t s) { return enqueue_apply(e, akey, s, 1); };
+        ks.push_back(k);
+    }
+    k.name = "adam_clipped";
+    k.flops = 13.0 * P;   // g * coef, then Adam
+    k.bytes = 4.0 * (7.0 * P + (soft ? 2.0 * P : 0.0));   // read g, p, m, v (+ target); write p, m, v (+ target)
+    k.run = [=](hipStream_t s) {
+        const int rc = enqueue_apply(e, akey, s, 2);
+        if (rc) return rc;
+        // dqnx_apply_grads' bookkeeping, here too so that an eagerly enqueued plan (dqnx_learn_step_timed)
+        // leaves it right: mode 2 changes the conv weights without their permuted copies, and the
+        // fused plan's blocked copies are current only if this pass wrote them
+        e->perm_dirty = true;
+        if (akey & KEY_KEEP_BLK) e->wblk_dirty = false;
+        else if (!adam_keeps_blk(e)) e->wblk_dirty = true;
+        return rc;
+    };
+    ks.push_back(k);
+    if ((key & DQNX_STEP_STATS) && e->stats_chunks) ks.push_back(stats_kstep(e, key));
+    return ks;
+}
+
+// a step's launches: the compute launches of the plan, then (DQNX_STEP_STATS) the statistics launch
+std::vector<KStep> build_learn_steps(dqnx_engine* e, int key) {
+    if (key & KEY_CLIP_TAIL) return clip_tail_steps(e, key);
+    if (key & KEY_CLIP) {
+        // gradient clipping: the gradient-only plan, then the tail.  With the in-launch draw
+        // (KEY_SAMPLE_NEXT) a minibatch is pending when the Adam pass runs: on the fused plan it
+        // writes the blocked copies itself, as dqnx_apply_grads does then
+        std::vector<KStep> ks =
+            build_compute_steps(e, (key & ~(KEY_CLIP | DQNX_STEP_STATS | DQNX_STEP_SOFT_UPDATE)) | DQNX_STEP_GRADS_ONLY);
+        const bool keep = e->bwd_plan == 2 && (key & KEY_SAMPLE_NEXT);
+        const std::vector<KStep> tail = clip_tail_steps(
+            e, KEY_CLIP_TAIL | (key & (DQNX_STEP_SOFT_UPDATE | DQNX_STEP_STATS | KEY_SLOT1)) | (keep ? KEY_KEEP_BLK | KEY_KEEP_MTC : 0));
+        ks.insert(ks.end(), tail.begin(), tail.end());
+        return ks;
+    }
+    std::vector<KStep> ks = build_compute_steps(e, key & ~DQNX_STEP_STATS);
+    if ((key & DQNX_STEP_STATS) && e->stats_chunks) ks.push_back(stats_kstep(e, key));
+    return ks;
 }
 
 // Capture `fn` (enqueueing on the given stream) into an executable graph.
@@ -2864,6 +2899,219 @@ int dp_buckets(dqnx_engine* e, std::vector<DpBucket>& out) {
     return DQNX_OK;
 }
 
+// ---- engine creation: everything decided from the configuration, up to the arena layout ----
+
+// what creation refuses before any plan is chosen
+static int check_config(const dqnx_engine* e) {
+    const dqnx_config& c = e->cfg;
+    if (c.algo < DQNX_ALGO_DQN || c.algo > DQNX_ALGO_PER_DOUBLE) return set_error(DQNX_EINVAL, "bad algo");
+    if (c.algo == DQNX_ALGO_PER_DOUBLE && c.per_numpy121) {
+        const int rc = per_numpy121_init();
+        if (rc) return rc;
+    }
+    if (c.algo == DQNX_ALGO_PER_DOUBLE) {
+        // exact float64 tree sums need cap <= 2^20 (see per.hip); one sampler workgroup <= PER_MAX_B
+        if (c.capacity > ((int64_t)1 << 20)) return set_error(DQNX_EUNSUPPORTED, "PER capacity > 2^20");
+        if (c.batch > PER_MAX_B) return set_error(DQNX_EUNSUPPORTED, "PER batch > %d", PER_MAX_B);
+    }
+    if (c.batch <= 0 || c.world_size <= 0 || c.rank < 0 || c.rank >= c.world_size || c.batch % c.world_size)
+        return set_error(DQNX_EINVAL, "batch must be a positive multiple of world_size");
+    if (c.capacity <= 0 || c.capacity >= ((int64_t)1 << 31)) return set_error(DQNX_EINVAL, "capacity out of range");
+    if (e->np.NH > 16) return set_error(DQNX_EUNSUPPORTED, "head with more than 16 outputs");
+    if (!head_supported(e->np.F)) return set_error(DQNX_EUNSUPPORTED, "head input width %d not in {64,128,256}", e->np.F);
+    for (size_t l = 0; l < e->np.dense.size(); l++)
+        if (e->np.dense[l].out % 4) return set_error(DQNX_EUNSUPPORTED, "hidden widths must be multiples of 4");
+    if (sample_hash_slots(c.batch) < 0) return set_error(DQNX_EUNSUPPORTED, "batch too large for the sampler");
+    return DQNX_OK;
+}
+
+// the step plan (dqnx_engine::bwd_plan): the fused MLP plan where its forward fits, else per-layer
+static int plan_step(dqnx_engine* e) {
+    const dqnx_config& c = e->cfg;
+    {
+        FusedFwdArgs& fp = e->fplan;
+        memset(&fp, 0, sizeof(fp));
+        fp.L = (int)e->np.dense.size();
+        for (int l = 0; l < fp.L && l < FUSED_MAX_L; l++) {
+            fp.in[l] = e->np.dense[l].in;
+            fp.out[l] = e->np.dense[l].out;
+        }
+        fp.NH = e->np.NH;
+        fp.F = e->np.F;
+        if (c.compute_dtype != DQNX_COMPUTE_FP32 && c.compute_dtype != DQNX_COMPUTE_BF16)
+            return set_error(DQNX_EINVAL, "bad compute_dtype %d", c.compute_dtype);
+        const bool bf = c.compute_dtype == DQNX_COMPUTE_BF16;
+        const bool fused_ok = c.net.kind == DQNX_NET_MLP && fused_fwd_plan(fp, c.net.obs_dim, bf, 1);
+        e->bwd_plan = fused_ok ? 2 : 0;
+        if (route_flag("DQNX_BWD_PLAN")) {
+            const int want = route_knob("DQNX_BWD_PLAN", 2);
+            if (want == 0 || (want == 1 && c.net.kind == DQNX_NET_MLP) || (want == 2 && fused_ok)) e->bwd_plan = want;
+        }
+        if (bf && e->bwd_plan != 2)   // bf16 lives in the fused MLP kernels only
+            return set_error(DQNX_EUNSUPPORTED, "bf16 compute needs the fused MLP plan (MLP, widths multiple of 64 <= 256, <= 3 layers)");
+    }
+    return DQNX_OK;
+}
+
+// the fused plan's forward shape: rows per workgroup, the opt-in split / paired layer-1 launches
+static void plan_fused_forward(dqnx_engine* e) {
+    const dqnx_config& c = e->cfg;
+    // forward rows per workgroup.  bf16: the largest of 4, 2 (x16) that still gives every
+    // CU a workgroup (each weight fragment streamed from L2 then feeds mr MFMAs): 30.5 ->
+    // 26.2 us at B=8192.  fp32 is MFMA-bound per CU and gains nothing (B=4096: 37.8 us at
+    // mr 1, 43.8 at 2, 41.0 at 4), so it keeps 16-row workgroups.
+    const int nst = c.algo == DQNX_ALGO_DQN ? 2 : 3;
+    int mr = 1;
+    if (e->fplan.bf16)
+        for (int cand : {4, 2})
+            if (mr == 1 && ((e->Bl + 16 * cand - 1) / (16 * cand)) * nst >= 256) mr = cand;
+    mr = route_knob("DQNX_FWD_MR", mr);
+    FusedFwdArgs trial = e->fplan;
+    if (mr != 1 && fused_fwd_plan(trial, c.net.obs_dim, e->fplan.bf16 != 0, mr)) e->fplan = trial;
+    // opt-in (DQNX_FWD_SPLIT=2|4): layer 1 in a launch of its own over 2 or 4 column parts
+    // per row tile.  Measured slower (B=1024: layer 1 alone 12.1 us on 384 workgroups vs
+    // 15.7 us for the whole one-launch forward; step 47.7 vs 45.2 us): the weight bytes
+    // streamed from L2 stay the same in total, so more workgroups do not help
+    if (e->fplan.mr == 1 && e->fplan.gw == 0 && e->np.dense.size() >= 2) {
+        if (route_flag("DQNX_FWD_SPLIT")) {
+            const int w = route_knob("DQNX_FWD_SPLIT", 1);
+            if (w <= 1) e->fsplit = 1;
+            else if (e->np.dense[0].out % (16 * w) == 0) e->fsplit = w;
+        }
+        // opt-in (DQNX_FWD_PAIR=1, fp32): the one-launch forward with layer 1's columns over two
+        // partner workgroups of one XCD and an in-launch sc1 hand-off of the H_1 halves (fused.hip)
+        bool pair_ok = e->np.dense[0].out % 32 == 0 && e->np.dense[0].out <= 32 * FUSED_WAVES;
+        for (size_t l = 1; l < e->np.dense.size(); l++) pair_ok = pair_ok && e->np.dense[l].out <= 16 * FUSED_WAVES;
+        if (e->fsplit <= 1 && !e->fplan.bf16 && route_knob("DQNX_FWD_PAIR", 0) != 0 && pair_ok) e->fpair = 1;
+        if (e->fsplit > 1) {   // layer 1's row tiles: 32 rows (each weight fragment feeds 2 MFMAs)
+            const int m = route_knob("DQNX_FWD_L1_MR", 2);
+            FusedFwdArgs t2 = e->fplan;
+            if ((m == 2 || m == 4) && fused_fwd_plan(t2, c.net.obs_dim, e->fplan.bf16 != 0, m)) e->fsplit_mr = m;
+        }
+    }
+}
+
+// the micro-CNN plan (micro.hip) where every conv fits it; it replaces the implicit-GEMM plan
+static void plan_micro(dqnx_engine* e) {
+    const dqnx_config& c = e->cfg;
+    const int NC = (int)e->np.conv.size();
+    MicroConv mc[MICRO_MAX_CONV];
+    const int nst = c.algo == DQNX_ALGO_DQN ? 2 : 3;
+    int S = 0, lf = 0, dS = 0, dlf = 0, lds_d[MICRO_MAX_CONV];
+    if (micro_geom(e->np, mc) && micro_plan(mc, NC, e->Bl, nst, e->n_cu, &S, &lf) &&
+        micro_dx_plan(mc, NC, e->Bl, &dS, lds_d, &dlf)) {
+        MicroDwArgs& d = e->micro_dw;
+        memset(&d, 0, sizeof(d));
+        d.nc = NC;
+        d.Bl = e->Bl;
+        for (int l = 0; l < NC; l++) {
+            MicroDwLayer& L = d.L[l];
+            L.Ci = mc[l].Ci; L.Hi = mc[l].Hi; L.Wi = mc[l].Wi; L.Co = mc[l].Co; L.Ho = mc[l].Ho; L.Wo = mc[l].Wo;
+            L.sh = mc[l].sh; L.sw = mc[l].sw;
+        }
+        if (micro_dw_plan(d, e->n_cu) == DQNX_OK) {
+            e->micro = true;
+            e->conv_ig = false;
+            e->micro_S = S;
+            e->micro_lds = lf;
+            e->micro_dx_S = dS;
+            e->micro_dx_lds = dlf;
+            for (int l = 0; l < NC; l++) e->micro_lds_d[l] = lds_d[l];
+        }
+    }
+}
+
+// split-K slabs of every conv's weight gradient
+static int plan_conv_slices(dqnx_engine* e) {
+    const int NC = (int)e->np.conv.size();
+    // conv dW workgroups to aim for: the (4,84,84) conv 1 ([32 x 37] tile grid 2 x 1) had only
+    // 64 workgroups at the old 32-slice cap; DQNX_CONV_DW_WGS=0 restores that rule
+    int dw_wgs = 1024;
+    dw_wgs = std::max(0, tuning_knob("DQNX_CONV_DW_WGS", dw_wgs));
+    for (int l = 0; l < NC; l++) {   // split-K over the conv's output pixels (b, ho, wo)
+        const ConvPlan& cq = e->np.conv[l];
+        const int rows = e->Bl * cq.Ho * cq.Wo;
+        int S = rows / 512;
+        if (S < 1) S = 1;
+        if (S > 32) S = 32;
+        const bool big = conv_dw_big(rows, cq.K);
+        const int tiles = big ? conv_dw_big_tiles(cq.K, cq.Co)
+                              : ((cq.K + 1 + BWD_TILE - 1) / BWD_TILE) * ((cq.Co + BWD_TILE - 1) / BWD_TILE);
+        if (dw_wgs > 0) S = std::max(S, std::min({rows / 512, (dw_wgs + tiles - 1) / tiles, 256}));
+        int ks = (int)align_up((uint64_t)((rows + S - 1) / S), 16);
+        S = (rows + ks - 1) / ks;
+        e->cslices[l] = S;
+        e->ckslice[l] = ks;
+        if (e->conv_ig) {   // slices of output row groups (k_conv_dw_ig)
+            ConvDwIgArgs d;
+            cig_dw_geom(cq, e->Bl, l == 0, d);
+            e->cslices[l] = d.slices;
+        }
+        if (e->micro) e->cslices[l] = e->micro_dw.L[l].slices;   // sample slices of k_micro_dw
+        if (e->np.conv[l].Co % 4) return set_error(DQNX_EUNSUPPORTED, "conv channels must be multiples of 4");
+    }
+    return DQNX_OK;
+}
+
+int plan_engine(dqnx_engine* e) {
+    const dqnx_config& c = e->cfg;
+    int rc = check_config(e);
+    if (rc) return rc;
+    rc = plan_step(e);
+    if (rc) return rc;
+    {   // the current device's compute units: the plans below size their grids (and the conv dW /
+        // dense-1 split-K slab counts, hence their fixed summation order) from it.  Without a visible
+        // device (host-only plan checks) the MI355X's 256 stays.
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
+            e->n_cu = cus;
+        (void)hipGetLastError();
+    }
+    e->Bg = c.batch;
+    e->Bl = c.batch / c.world_size;
+    e->local_sampling = c.local_sampling && c.world_size > 1;
+    if (e->local_sampling && c.algo == DQNX_ALGO_PER_DOUBLE)   // the replicated SumTree needs every rank to apply the same ordered updates
+        return set_error(DQNX_EUNSUPPORTED, "rank-local sampling is for uniform replay (PER samples globally)");
+    e->shard_begin = e->local_sampling ? 0 : c.rank * e->Bl;
+    e->Bs = e->local_sampling ? e->Bl : e->Bg;
+    e->stride = (int)align_up((uint64_t)c.net.obs_dim, 4);
+    e->tiles = (e->Bl + 15) / 16;
+    if (e->bwd_plan == 2) plan_fused_forward(e);
+    e->setsize = sample_setsize(e->Bs);
+    const int L = (int)e->np.dense.size();
+    e->slices.assign(L, 1);
+    e->kslice.assign(L, e->Bl);
+    // minibatch rows per split-K slice of the weight gradients.  bf16 (configs[4], B=8192): 512 rows
+    // = 16 slabs, the Adam pass sums half the partials (step 94-96 -> 92 us, profiles/r04/dw_bf16_shapes.json)
+    int dw_rows = (e->bwd_plan == 2 && e->fplan.bf16) ? 512 : 256;
+    dw_rows = std::max(16, tuning_knob("DQNX_DW_ROWS", dw_rows));
+    for (int l = 0; l < L; l++) {
+        int S = e->Bl / dw_rows;
+        if (S < 1) S = 1;
+        if (S > 32) S = 32;
+        int ks = (int)align_up((uint64_t)((e->Bl + S - 1) / S), 16);
+        S = (e->Bl + ks - 1) / ks;
+        e->slices[l] = S;
+        e->kslice[l] = ks;
+    }
+    // opt-in (DQNX_DWB_T=1): bf16 weight gradients from slab-transposed copies written by the forward
+    // (the one-launch plan) and the head kernel (k_dw_bf16d; measured slower at configs[4], fused.hip);
+    // whole 32-sample chunks
+    e->dwt = e->bwd_plan == 2 && e->fplan.bf16 && !(e->fsplit > 1 && e->fplan.mr == 1) && e->Bl % 32 == 0 &&
+             e->kslice[0] % 32 == 0 && e->kslice[0] <= 512 && route_knob("DQNX_DWB_T", 0) != 0;
+    const int NC = (int)e->np.conv.size();
+    e->cslices.assign(NC, 1);
+    e->ckslice.assign(NC, 1);
+    e->conv_ig = conv_ig_plan(e->np, e->Bl);
+    if (NC && route_knob("DQNX_MICRO_CNN", 1) != 0) plan_micro(e);   // DQNX_MICRO_CNN=0 keeps the per-layer conv kernels
+    if (NC && route_knob("DQNX_F1_SPLITK", 1) != 0) {   // dense 1 (K = F) as 64 x 64 split-K tiles
+        const int nst = c.algo == DQNX_ALGO_DQN ? 2 : 3;
+        e->f1_ksplit = fwd_split_ksplit(e->Bl, e->np.dense[0].out, e->np.dense[0].in, nst, e->n_cu, &e->f1_kchunk);
+    }
+    return plan_conv_slices(e);
+}
+
 }  // namespace
 
 // ======================================================================================
@@ -2921,196 +3169,14 @@ void dqnx_config_defaults(dqnx_config* c) {
 int dqnx_engine_create(const dqnx_config* cfg, dqnx_engine** out) {
     if (!cfg || !out) return set_error(DQNX_EINVAL, "null argument");
     *out = nullptr;
-    dqnx_engine* e = new dqnx_engine();
+    std::unique_ptr<dqnx_engine> e(new dqnx_engine());   // (freed by every refusal below)
     e->cfg = *cfg;
     int rc = plan_net(&cfg->net, e->np);
-    if (rc) { delete e; return rc; }
-    const dqnx_config c = *cfg;   // a copy: the error paths below read it after `delete e`
-    if (c.algo < DQNX_ALGO_DQN || c.algo > DQNX_ALGO_PER_DOUBLE) { delete e; return set_error(DQNX_EINVAL, "bad algo"); }
-    if (c.algo == DQNX_ALGO_PER_DOUBLE && c.per_numpy121) {
-        rc = per_numpy121_init();
-        if (rc) { delete e; return rc; }
-    }
-    if (c.algo == DQNX_ALGO_PER_DOUBLE) {
-        // exact float64 tree sums need cap <= 2^20 (see per.hip); one sampler workgroup <= PER_MAX_B
-        if (c.capacity > ((int64_t)1 << 20)) { delete e; return set_error(DQNX_EUNSUPPORTED, "PER capacity > 2^20"); }
-        if (c.batch > PER_MAX_B) { delete e; return set_error(DQNX_EUNSUPPORTED, "PER batch > %d", PER_MAX_B); }
-    }
-    if (c.batch <= 0 || c.world_size <= 0 || c.rank < 0 || c.rank >= c.world_size || c.batch % c.world_size)
-        { delete e; return set_error(DQNX_EINVAL, "batch must be a positive multiple of world_size"); }
-    if (c.capacity <= 0 || c.capacity >= ((int64_t)1 << 31)) { delete e; return set_error(DQNX_EINVAL, "capacity out of range"); }
-    if (e->np.NH > 16) { delete e; return set_error(DQNX_EUNSUPPORTED, "head with more than 16 outputs"); }
-    if (!head_supported(e->np.F)) {
-        const int F = e->np.F;   // (read before the delete: found by the ASan plan check)
-        delete e;
-        return set_error(DQNX_EUNSUPPORTED, "head input width %d not in {64,128,256}", F);
-    }
-    for (size_t l = 0; l < e->np.dense.size(); l++)
-        if (e->np.dense[l].out % 4) { delete e; return set_error(DQNX_EUNSUPPORTED, "hidden widths must be multiples of 4"); }
-    if (sample_hash_slots(c.batch) < 0) { delete e; return set_error(DQNX_EUNSUPPORTED, "batch too large for the sampler"); }
-    {
-        FusedFwdArgs& fp = e->fplan;
-        memset(&fp, 0, sizeof(fp));
-        fp.L = (int)e->np.dense.size();
-        for (int l = 0; l < fp.L && l < FUSED_MAX_L; l++) {
-            fp.in[l] = e->np.dense[l].in;
-            fp.out[l] = e->np.dense[l].out;
-        }
-        fp.NH = e->np.NH;
-        fp.F = e->np.F;
-        if (c.compute_dtype != DQNX_COMPUTE_FP32 && c.compute_dtype != DQNX_COMPUTE_BF16)
-            { delete e; return set_error(DQNX_EINVAL, "bad compute_dtype %d", c.compute_dtype); }
-        const bool bf = c.compute_dtype == DQNX_COMPUTE_BF16;
-        const bool fused_ok = c.net.kind == DQNX_NET_MLP && fused_fwd_plan(fp, c.net.obs_dim, bf, 1);
-        e->bwd_plan = fused_ok ? 2 : 0;
-        if (route_flag("DQNX_BWD_PLAN")) {
-            const int want = route_knob("DQNX_BWD_PLAN", 2);
-            if (want == 0 || (want == 1 && c.net.kind == DQNX_NET_MLP) || (want == 2 && fused_ok)) e->bwd_plan = want;
-        }
-        if (bf && e->bwd_plan != 2) {   // bf16 lives in the fused MLP kernels only
-            delete e;
-            return set_error(DQNX_EUNSUPPORTED, "bf16 compute needs the fused MLP plan (MLP, widths multiple of 64 <= 256, <= 3 layers)");
-        }
-    }
-    {   // the current device's compute units: the plans below size their grids (and the conv dW /
-        // dense-1 split-K slab counts, hence their fixed summation order) from it.  Without a visible
-        // device (host-only plan checks) the MI355X's 256 stays.
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-            e->n_cu = cus;
-        (void)hipGetLastError();
-    }
-    e->Bg = c.batch;
-    e->Bl = c.batch / c.world_size;
-    e->local_sampling = c.local_sampling && c.world_size > 1;
-    if (e->local_sampling && c.algo == DQNX_ALGO_PER_DOUBLE) {
-        delete e;   // the replicated SumTree needs every rank to apply the same ordered updates
-        return set_error(DQNX_EUNSUPPORTED, "rank-local sampling is for uniform replay (PER samples globally)");
-    }
-    e->shard_begin = e->local_sampling ? 0 : c.rank * e->Bl;
-    e->Bs = e->local_sampling ? e->Bl : e->Bg;
-    e->stride = (int)align_up((uint64_t)c.net.obs_dim, 4);
-    e->tiles = (e->Bl + 15) / 16;
-    if (e->bwd_plan == 2) {
-        // forward rows per workgroup.  bf16: the largest of 4, 2 (x16) that still gives every
-        // CU a workgroup (each weight fragment streamed from L2 then feeds mr MFMAs): 30.5 ->
-        // 26.2 us at B=8192.  fp32 is MFMA-bound per CU and gains nothing (B=4096: 37.8 us at
-        // mr 1, 43.8 at 2, 41.0 at 4), so it keeps 16-row workgroups.
-        const int nst = c.algo == DQNX_ALGO_DQN ? 2 : 3;
-        int mr = 1;
-        if (e->fplan.bf16)
-            for (int cand : {4, 2})
-                if (mr == 1 && ((e->Bl + 16 * cand - 1) / (16 * cand)) * nst >= 256) mr = cand;
-        mr = route_knob("DQNX_FWD_MR", mr);
-        FusedFwdArgs trial = e->fplan;
-        if (mr != 1 && fused_fwd_plan(trial, c.net.obs_dim, e->fplan.bf16 != 0, mr)) e->fplan = trial;
-        // opt-in (DQNX_FWD_SPLIT=2|4): layer 1 in a launch of its own over 2 or 4 column parts
-        // per row tile.  Measured slower (B=1024: layer 1 alone 12.1 us on 384 workgroups vs
-        // 15.7 us for the whole one-launch forward; step 47.7 vs 45.2 us): the weight bytes
-        // streamed from L2 stay the same in total, so more workgroups do not help
-        if (e->fplan.mr == 1 && e->fplan.gw == 0 && e->np.dense.size() >= 2) {
-            if (route_flag("DQNX_FWD_SPLIT")) {
-                const int w = route_knob("DQNX_FWD_SPLIT", 1);
-                if (w <= 1) e->fsplit = 1;
-                else if (e->np.dense[0].out % (16 * w) == 0) e->fsplit = w;
-            }
-            // opt-in (DQNX_FWD_PAIR=1, fp32): the one-launch forward with layer 1's columns over two
-            // partner workgroups of one XCD and an in-launch sc1 hand-off of the H_1 halves (fused.hip)
-            bool pair_ok = e->np.dense[0].out % 32 == 0 && e->np.dense[0].out <= 32 * FUSED_WAVES;
-            for (size_t l = 1; l < e->np.dense.size(); l++) pair_ok = pair_ok && e->np.dense[l].out <= 16 * FUSED_WAVES;
-            if (e->fsplit <= 1 && !e->fplan.bf16 && route_knob("DQNX_FWD_PAIR", 0) != 0 && pair_ok) e->fpair = 1;
-            if (e->fsplit > 1) {   // layer 1's row tiles: 32 rows (each weight fragment feeds 2 MFMAs)
-                const int m = route_knob("DQNX_FWD_L1_MR", 2);
-                FusedFwdArgs t2 = e->fplan;
-                if ((m == 2 || m == 4) && fused_fwd_plan(t2, c.net.obs_dim, e->fplan.bf16 != 0, m)) e->fsplit_mr = m;
-            }
-        }
-    }
-    e->setsize = sample_setsize(e->Bs);
-    const int L = (int)e->np.dense.size();
-    e->slices.assign(L, 1);
-    e->kslice.assign(L, e->Bl);
-    // minibatch rows per split-K slice of the weight gradients.  bf16 (configs[4], B=8192): 512 rows
-    // = 16 slabs, the Adam pass sums half the partials (step 94-96 -> 92 us, profiles/r04/dw_bf16_shapes.json)
-    int dw_rows = (e->bwd_plan == 2 && e->fplan.bf16) ? 512 : 256;
-    dw_rows = std::max(16, tuning_knob("DQNX_DW_ROWS", dw_rows));
-    for (int l = 0; l < L; l++) {
-        int S = e->Bl / dw_rows;
-        if (S < 1) S = 1;
-        if (S > 32) S = 32;
-        int ks = (int)align_up((uint64_t)((e->Bl + S - 1) / S), 16);
-        S = (e->Bl + ks - 1) / ks;
-        e->slices[l] = S;
-        e->kslice[l] = ks;
-    }
-    // opt-in (DQNX_DWB_T=1): bf16 weight gradients from slab-transposed copies written by the forward
-    // (the one-launch plan) and the head kernel (k_dw_bf16d; measured slower at configs[4], fused.hip);
-    // whole 32-sample chunks
-    e->dwt = e->bwd_plan == 2 && e->fplan.bf16 && !(e->fsplit > 1 && e->fplan.mr == 1) && e->Bl % 32 == 0 &&
-             e->kslice[0] % 32 == 0 && e->kslice[0] <= 512 && route_knob("DQNX_DWB_T", 0) != 0;
-    const int NC = (int)e->np.conv.size();
-    e->cslices.assign(NC, 1);
-    e->ckslice.assign(NC, 1);
-    e->conv_ig = conv_ig_plan(e->np, e->Bl);
-    if (NC && route_knob("DQNX_MICRO_CNN", 1) != 0) {   // DQNX_MICRO_CNN=0 keeps the per-layer conv kernels
-        MicroConv mc[MICRO_MAX_CONV];
-        const int nst = c.algo == DQNX_ALGO_DQN ? 2 : 3;
-        int S = 0, lf = 0, dS = 0, dlf = 0, lds_d[MICRO_MAX_CONV];
-        if (micro_geom(e->np, mc) && micro_plan(mc, NC, e->Bl, nst, e->n_cu, &S, &lf) &&
-            micro_dx_plan(mc, NC, e->Bl, &dS, lds_d, &dlf)) {
-            MicroDwArgs& d = e->micro_dw;
-            memset(&d, 0, sizeof(d));
-            d.nc = NC;
-            d.Bl = e->Bl;
-            for (int l = 0; l < NC; l++) {
-                MicroDwLayer& L = d.L[l];
-                L.Ci = mc[l].Ci; L.Hi = mc[l].Hi; L.Wi = mc[l].Wi; L.Co = mc[l].Co; L.Ho = mc[l].Ho; L.Wo = mc[l].Wo;
-                L.sh = mc[l].sh; L.sw = mc[l].sw;
-            }
-            if (micro_dw_plan(d, e->n_cu) == DQNX_OK) {
-                e->micro = true;
-                e->conv_ig = false;
-                e->micro_S = S;
-                e->micro_lds = lf;
-                e->micro_dx_S = dS;
-                e->micro_dx_lds = dlf;
-                for (int l = 0; l < NC; l++) e->micro_lds_d[l] = lds_d[l];
-            }
-        }
-    }
-    if (NC && route_knob("DQNX_F1_SPLITK", 1) != 0) {   // dense 1 (K = F) as 64 x 64 split-K tiles
-        const int nst = c.algo == DQNX_ALGO_DQN ? 2 : 3;
-        e->f1_ksplit = fwd_split_ksplit(e->Bl, e->np.dense[0].out, e->np.dense[0].in, nst, e->n_cu, &e->f1_kchunk);
-    }
-    // conv dW workgroups to aim for: the (4,84,84) conv 1 ([32 x 37] tile grid 2 x 1) had only
-    // 64 workgroups at the old 32-slice cap; DQNX_CONV_DW_WGS=0 restores that rule
-    int dw_wgs = 1024;
-    dw_wgs = std::max(0, tuning_knob("DQNX_CONV_DW_WGS", dw_wgs));
-    for (int l = 0; l < NC; l++) {   // split-K over the conv's output pixels (b, ho, wo)
-        const ConvPlan& cq = e->np.conv[l];
-        const int rows = e->Bl * cq.Ho * cq.Wo;
-        int S = rows / 512;
-        if (S < 1) S = 1;
-        if (S > 32) S = 32;
-        const bool big = conv_dw_big(rows, cq.K);
-        const int tiles = big ? conv_dw_big_tiles(cq.K, cq.Co)
-                              : ((cq.K + 1 + BWD_TILE - 1) / BWD_TILE) * ((cq.Co + BWD_TILE - 1) / BWD_TILE);
-        if (dw_wgs > 0) S = std::max(S, std::min({rows / 512, (dw_wgs + tiles - 1) / tiles, 256}));
-        int ks = (int)align_up((uint64_t)((rows + S - 1) / S), 16);
-        S = (rows + ks - 1) / ks;
-        e->cslices[l] = S;
-        e->ckslice[l] = ks;
-        if (e->conv_ig) {   // slices of output row groups (k_conv_dw_ig)
-            ConvDwIgArgs d;
-            cig_dw_geom(cq, e->Bl, l == 0, d);
-            e->cslices[l] = d.slices;
-        }
-        if (e->micro) e->cslices[l] = e->micro_dw.L[l].slices;   // sample slices of k_micro_dw
-        if (e->np.conv[l].Co % 4) { delete e; return set_error(DQNX_EUNSUPPORTED, "conv channels must be multiples of 4"); }
-    }
-    layout(e);
-    *out = e;
+    if (rc) return rc;
+    rc = plan_engine(e.get());
+    if (rc) return rc;
+    layout(e.get());
+    *out = e.release();
     return DQNX_OK;
 }
 
@@ -3608,8 +3674,6 @@ static int learn_step_side_fused(dqnx_engine* e, int base, bool prefetch, hipStr
     return DQNX_OK;
 }
 
-static int learn_step_clipped(dqnx_engine* e, int32_t flags, hipStream_t s);
-
 static int learn_step_impl(dqnx_engine* e, int32_t flags, void* stream) {
     int rc = check_bound(e);
     if (rc) return rc;
@@ -3678,14 +3742,6 @@ static int learn_step_impl(dqnx_engine* e, int32_t flags, void* stream) {
     return DQNX_OK;
 }
 
-int dqnx_learn_step(dqnx_engine* e, int32_t flags, void* stream) {
-    int rc = check_bound(e);
-    if (rc) return rc;
-    // gradient clipping: a whole step is its gradient-only half, the clipping tail, the Adam half
-    if (clip_on(e) && !(flags & DQNX_STEP_GRADS_ONLY)) return learn_step_clipped(e, flags, (hipStream_t)stream);
-    return learn_step_impl(e, flags, stream);
-}
-
 // The second half of a step from DQNX_BUF_GRADS: dqnx_apply_grads (clip: with the clipping tail in
 // front and the coefficient in the Adam launch; stats_slot >= 0: a clipped learn step's statistics
 // launch behind it, reading the (idx, phys) pair of that slot).
@@ -3695,10 +3751,10 @@ static int apply_impl(dqnx_engine* e, int32_t flags, bool clip, int stats_slot, 
     // relayout launch); otherwise the next sampler launch rebuilds them for free
     // (the side-stream pipeline too: its next step has no sampler launch on the compute stream)
     const bool keep = e->bwd_plan == 2 && e->pf_valid && (e->pf_inlaunch || route_knob("DQNX_SIDE_APPLY_KEEP", 1) != 0);
-    const int key = 0x100 | (flags & DQNX_STEP_SOFT_UPDATE) | (keep ? 0x200 : 0) | (keep && e->pf_inlaunch ? 0x400 : 0);
+    const int key = KEY_SLOT1 | (flags & DQNX_STEP_SOFT_UPDATE) | (keep ? KEY_KEEP_BLK : 0) | (keep && e->pf_inlaunch ? KEY_KEEP_MTC : 0);
     int rc2;
     if (clip) {
-        const int tkey = KEY_CLIP_TAIL | (key & ~0x100) | (stats_slot >= 0 ? DQNX_STEP_STATS | (stats_slot << 8) : 0);
+        const int tkey = KEY_CLIP_TAIL | (key & ~KEY_SLOT1) | (stats_slot >= 0 ? DQNX_STEP_STATS | (stats_slot << 8) : 0);
         const std::vector<KStep>& ks = steps_for(e, tkey);
         rc2 = run_graphed(e, 0x20000000 | tkey, stream, [&](hipStream_t s) { return enqueue_range(ks, 0, (int)ks.size(), s); });
     } else {
@@ -3740,6 +3796,14 @@ static int learn_step_clipped(dqnx_engine* e, int32_t flags, hipStream_t s) {
     if (stats && e->bwd_plan != 2 && e->ev_computed[slot] && e->pf_computed_valid[slot])
         DQNX_HIP_CHECK(hipEventRecord(e->ev_computed[slot], s));
     return DQNX_OK;
+}
+
+int dqnx_learn_step(dqnx_engine* e, int32_t flags, void* stream) {
+    int rc = check_bound(e);
+    if (rc) return rc;
+    // gradient clipping: a whole step is its gradient-only half, the clipping tail, the Adam half
+    if (clip_on(e) && !(flags & DQNX_STEP_GRADS_ONLY)) return learn_step_clipped(e, flags, (hipStream_t)stream);
+    return learn_step_impl(e, flags, stream);
 }
 
 // `count` consecutive learn steps as ONE graph (pure learning loops, e.g. several learn steps
@@ -4162,10 +4226,99 @@ int dqnx_hard_update(dqnx_engine* e, void* stream) {
     return DQNX_OK;
 }
 
+static void act_conv_args(const ConvPlan& cp, ActConvArgs& ca) {
+    memset(&ca, 0, sizeof(ca));
+    ca.Ci = cp.Ci; ca.Hi = cp.Hi; ca.Wi = cp.Wi; ca.Co = cp.Co; ca.Ho = cp.Ho; ca.Wo = cp.Wo;
+    ca.kh = cp.kh; ca.kw = cp.kw; ca.sh = cp.sh; ca.sw = cp.sw; ca.ph = cp.ph; ca.pw = cp.pw;
+}
+
+// The large route (act_large.hip) of a planned net, for calls of n rows.  Rows go through in chunks of at
+// most kActWideRows, each chunk reusing the scratch in stream order:
+//   [conv outputs of every conv but the last, Rc rows][F = dense input, Rc rows (two-stream nets)]
+//   [dense 1's split-K shares S x Rc x J][h1 Rc x J] -- `bytes` so far, a multiple of 256 --
+//   then the MLP acting kernel's part for layers 2..L on Rc rows (its tickets at the END of the buffer)
+// with Rc = min(n, kActWideRows).  `tail`: the net's layer tables shifted by one (input h1, D = out[0]).
+struct ActLargeLayout {
+    int Rc, S, Ls;
+    uint64_t F_off, part_off, h_off, bytes, mlp;
+    ActArgs tail;
+};
+static void act_large_layout(const dqnx_net_desc* net, const NetPlan& np, const ActArgs& a, int n, ActLargeLayout& y) {
+    const auto up = [](uint64_t b, uint64_t q) { return (b + q - 1) / q * q; };
+    y.Rc = std::max(0, std::min(n, kActWideRows));
+    act_wide_slices(a.D, &y.S, &y.Ls);
+    const uint64_t Rc = (uint64_t)y.Rc, J = (uint64_t)a.out[0];
+    uint64_t b = 0;
+    for (size_t l = 0; l + 1 < np.conv.size(); l++) b += Rc * np.conv[l].Co * np.conv[l].Ho * np.conv[l].Wo * 4;
+    y.F_off = b = up(b, 16);
+    if (net->kind != DQNX_NET_MLP) b += Rc * a.D * 4;
+    y.part_off = b = up(b, 16);
+    b += (uint64_t)y.S * Rc * J * 4;
+    y.h_off = b = up(b, 16);
+    b += Rc * J * 4;
+    y.bytes = up(b, 256);
+    ActArgs& t = y.tail;
+    t = a;
+    t.large = 0;
+    t.L = a.L - 1;
+    t.D = a.out[0];
+    t.ld = std::max(t.D, t.A);
+    for (int l = 0; l < t.L; l++) {
+        t.in[l] = a.in[l + 1]; t.out[l] = a.out[l + 1]; t.off[l] = a.off[l + 1];
+        t.ld = std::max(t.ld, t.out[l]);
+    }
+    t.ld = (t.ld + 3) & ~3;
+    y.mlp = t.L >= 1 ? act_scratch_bytes(y.Rc, t.out[0], t.ld, t.L, t.L >= 2 ? t.out[1] : 0) : 0;
+}
+
 // acting kernel geometry of a network (host only).  A two-stream net acts as its convs (one launch
 // for the whole stack where act_ts_plan applies, else one each; act_hybrid.hip) followed by the MLP
 // acting kernel on F = cat(flatten(conv), macro).
-static int act_plan_build(const dqnx_net_desc* net, NetPlan& np, ActArgs& a, int large_mode);
+static int act_plan_build(const dqnx_net_desc* net, NetPlan& np, ActArgs& a, int large_mode) {
+    int rc = plan_net(net, np);
+    if (rc) return rc;
+    memset(&a, 0, sizeof(a));
+    a.D = net->kind == DQNX_NET_MLP ? net->obs_dim : np.dense[0].in;
+    a.L = (int)np.dense.size(); a.A = net->n_actions; a.F = np.F;
+    if (a.L > kActMaxDense) return set_error(DQNX_EUNSUPPORTED, "dqnx_act: more than %d dense layers", kActMaxDense);
+    a.dueling = net->head == DQNX_HEAD_DUELING; a.act = net->activation;
+    a.ld = std::max(a.D, a.A);
+    for (int l = 0; l < a.L; l++) {
+        a.in[l] = np.dense[l].in; a.out[l] = np.dense[l].out; a.off[l] = np.dense[l].off;
+        a.ld = std::max(a.ld, a.out[l]);
+    }
+    a.ld = (a.ld + 3) & ~3;   // float4 LDS rows
+    a.head_off = np.head_off;
+    // the large route: forced (2), or taken by a net the LDS-resident kernels refuse for its size (1)
+    bool large = large_mode == 2 && a.L >= 1;
+    if (large_mode == 1 && a.L >= 1 && act_rows_per_block(1, a.ld) == 0) large = true;
+    for (const ConvPlan& cp : np.conv) {   // each conv's row image + one channel's weights in LDS
+        ActConvArgs ca;
+        act_conv_args(cp, ca);
+        if (act_conv_lds_bytes(ca) > 64 * 1024) {
+            if (large_mode == 0)
+                return set_error(DQNX_EUNSUPPORTED, "dqnx_act: conv input %dx%dx%d too large for the acting kernel",
+                                 cp.Ci, cp.Hi, cp.Wi);
+            large = true;
+        }
+    }
+    if (large) {
+        ActBandPlan bp;
+        for (const ConvPlan& cp : np.conv) {
+            ActConvArgs ca;
+            act_conv_args(cp, ca);
+            if (!act_band_plan(ca, bp))
+                return set_error(DQNX_EUNSUPPORTED, "dqnx_act: conv window %dx%d too large for the banded acting kernel",
+                                 cp.kh, cp.kw);
+        }
+        ActLargeLayout y;
+        act_large_layout(net, np, a, 1, y);
+        if (y.tail.L >= 1 && act_rows_per_block(1, y.tail.ld) == 0)
+            return set_error(DQNX_EUNSUPPORTED, "dqnx_act: layer width %d does not fit LDS", y.tail.ld);
+        a.large = 1;
+    }
+    return DQNX_OK;
+}
 
 // DQNX_ACT_LARGE, read at plan time: 0 (default) nets that do not fit LDS are refused; 1 they take the
 // large route (act_large.hip) and nets that fit keep their kernels; 2 every net takes the large route
@@ -4213,97 +4366,6 @@ static int act_plan(const dqnx_net_desc* net, const NetPlan** npp, ActArgs& a) {
     if (en.rc) return en.rc;
     *npp = &en.np;
     a = en.a;
-    return DQNX_OK;
-}
-
-static void act_conv_args(const ConvPlan& cp, ActConvArgs& ca) {
-    memset(&ca, 0, sizeof(ca));
-    ca.Ci = cp.Ci; ca.Hi = cp.Hi; ca.Wi = cp.Wi; ca.Co = cp.Co; ca.Ho = cp.Ho; ca.Wo = cp.Wo;
-    ca.kh = cp.kh; ca.kw = cp.kw; ca.sh = cp.sh; ca.sw = cp.sw; ca.ph = cp.ph; ca.pw = cp.pw;
-}
-
-// The large route (act_large.hip) of a planned net, for calls of n rows.  Rows go through in chunks of at
-// most kActWideRows, each chunk reusing the scratch in stream order:
-//   [conv outputs of every conv but the last, Rc rows][F = dense input, Rc rows (two-stream nets)]
-//   [dense 1's split-K shares S x Rc x J][h1 Rc x J] -- `bytes` so far, a multiple of 256 --
-//   then the MLP acting kernel's part for layers 2..L on Rc rows (its tickets at the END of the buffer)
-// with Rc = min(n, kActWideRows).  `tail`: the net's layer tables shifted by one (input h1, D = out[0]).
-struct ActLargeLayout {
-    int Rc, S, Ls;
-    uint64_t F_off, part_off, h_off, bytes, mlp;
-    ActArgs tail;
-};
-static void act_large_layout(const dqnx_net_desc* net, const NetPlan& np, const ActArgs& a, int n, ActLargeLayout& y) {
-    const auto up = [](uint64_t b, uint64_t q) { return (b + q - 1) / q * q; };
-    y.Rc = std::max(0, std::min(n, kActWideRows));
-    act_wide_slices(a.D, &y.S, &y.Ls);
-    const uint64_t Rc = (uint64_t)y.Rc, J = (uint64_t)a.out[0];
-    uint64_t b = 0;
-    for (size_t l = 0; l + 1 < np.conv.size(); l++) b += Rc * np.conv[l].Co * np.conv[l].Ho * np.conv[l].Wo * 4;
-    y.F_off = b = up(b, 16);
-    if (net->kind != DQNX_NET_MLP) b += Rc * a.D * 4;
-    y.part_off = b = up(b, 16);
-    b += (uint64_t)y.S * Rc * J * 4;
-    y.h_off = b = up(b, 16);
-    b += Rc * J * 4;
-    y.bytes = up(b, 256);
-    ActArgs& t = y.tail;
-    t = a;
-    t.large = 0;
-    t.L = a.L - 1;
-    t.D = a.out[0];
-    t.ld = std::max(t.D, t.A);
-    for (int l = 0; l < t.L; l++) {
-        t.in[l] = a.in[l + 1]; t.out[l] = a.out[l + 1]; t.off[l] = a.off[l + 1];
-        t.ld = std::max(t.ld, t.out[l]);
-    }
-    t.ld = (t.ld + 3) & ~3;
-    y.mlp = t.L >= 1 ? act_scratch_bytes(y.Rc, t.out[0], t.ld, t.L, t.L >= 2 ? t.out[1] : 0) : 0;
-}
-
-static int act_plan_build(const dqnx_net_desc* net, NetPlan& np, ActArgs& a, int large_mode) {
-    int rc = plan_net(net, np);
-    if (rc) return rc;
-    memset(&a, 0, sizeof(a));
-    a.D = net->kind == DQNX_NET_MLP ? net->obs_dim : np.dense[0].in;
-    a.L = (int)np.dense.size(); a.A = net->n_actions; a.F = np.F;
-    if (a.L > kActMaxDense) return set_error(DQNX_EUNSUPPORTED, "dqnx_act: more than %d dense layers", kActMaxDense);
-    a.dueling = net->head == DQNX_HEAD_DUELING; a.act = net->activation;
-    a.ld = std::max(a.D, a.A);
-    for (int l = 0; l < a.L; l++) {
-        a.in[l] = np.dense[l].in; a.out[l] = np.dense[l].out; a.off[l] = np.dense[l].off;
-        a.ld = std::max(a.ld, a.out[l]);
-    }
-    a.ld = (a.ld + 3) & ~3;   // float4 LDS rows
-    a.head_off = np.head_off;
-    // the large route: forced (2), or taken by a net the LDS-resident kernels refuse for its size (1)
-    bool large = large_mode == 2 && a.L >= 1;
-    if (large_mode == 1 && a.L >= 1 && act_rows_per_block(1, a.ld) == 0) large = true;
-    for (const ConvPlan& cp : np.conv) {   // each conv's row image + one channel's weights in LDS
-        ActConvArgs ca;
-        act_conv_args(cp, ca);
-        if (act_conv_lds_bytes(ca) > 64 * 1024) {
-            if (large_mode == 0)
-                return set_error(DQNX_EUNSUPPORTED, "dqnx_act: conv input %dx%dx%d too large for the acting kernel",
-                                 cp.Ci, cp.Hi, cp.Wi);
-            large = true;
-        }
-    }
-    if (large) {
-        ActBandPlan bp;
-        for (const ConvPlan& cp : np.conv) {
-            ActConvArgs ca;
-            act_conv_args(cp, ca);
-            if (!act_band_plan(ca, bp))
-                return set_error(DQNX_EUNSUPPORTED, "dqnx_act: conv window %dx%d too large for the banded acting kernel",
-                                 cp.kh, cp.kw);
-        }
-        ActLargeLayout y;
-        act_large_layout(net, np, a, 1, y);
-        if (y.tail.L >= 1 && act_rows_per_block(1, y.tail.ld) == 0)
-            return set_error(DQNX_EUNSUPPORTED, "dqnx_act: layer width %d does not fit LDS", y.tail.ld);
-        a.large = 1;
-    }
     return DQNX_OK;
 }
 
@@ -4407,16 +4469,6 @@ static bool act_host_direct(const dqnx_net_desc* net, int32_t n) {
     return n <= act_rows_per_block(n, a.ld) && act_ts_plan(*npp, n, sa);
 }
 
-// done_flag: the MLP acting kernel stores done_seq there (system scope) after the actions (dqnx_act_host)
-static int act_impl(const dqnx_net_desc* net, const float* params, const float* obs, int32_t n, int32_t* actions,
-                    float* values, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t* done_flag,
-                    uint32_t done_seq, bool* signals = nullptr);
-
-int dqnx_act(const dqnx_net_desc* net, const float* params, const float* obs, int32_t n, int32_t* actions,
-             float* values, void* scratch, uint64_t scratch_bytes, void* stream) {
-    return act_impl(net, params, obs, n, actions, values, scratch, scratch_bytes, stream, nullptr, 0);
-}
-
 // The large route (DQNX_ACT_LARGE; act_large.hip): chunks of at most kActWideRows rows, each a launch per
 // conv (banded), dense 1 (split-K weight stream), its reduce, and the rest of the net on h1 -- the MLP
 // acting kernel with the layer tables shifted by one, or the head kernel of a one-dense-layer net.  The
@@ -4487,9 +4539,10 @@ static int act_large_impl(const dqnx_net_desc* net, const NetPlan& np, const Act
     return DQNX_OK;
 }
 
+// done_flag: the MLP acting kernel stores done_seq there (system scope) after the actions (dqnx_act_host)
 static int act_impl(const dqnx_net_desc* net, const float* params, const float* obs, int32_t n, int32_t* actions,
                     float* values, void* scratch, uint64_t scratch_bytes, void* stream, uint32_t* done_flag,
-                    uint32_t done_seq, bool* signals) {
+                    uint32_t done_seq, bool* signals = nullptr) {
     const NetPlan* npp = nullptr;
     ActArgs a;
     if (signals) *signals = false;
@@ -4575,10 +4628,12 @@ static int act_impl(const dqnx_net_desc* net, const float* params, const float* 
     return launch_act(a, s);
 }
 
-// ---- drop-in Agent fast path ------------------------------------------------------------
-int dqnx_rng_sample_words(const uint32_t* state625, int64_t n, int32_t k, uint32_t* out625, int64_t* words);
-int dqnx_rng_advance(const uint32_t* state625, int64_t words, uint32_t* out625);
+int dqnx_act(const dqnx_net_desc* net, const float* params, const float* obs, int32_t n, int32_t* actions,
+             float* values, void* scratch, uint64_t scratch_bytes, void* stream) {
+    return act_impl(net, params, obs, n, actions, values, scratch, scratch_bytes, stream, nullptr, 0);
+}
 
+// ---- drop-in Agent fast path ------------------------------------------------------------
 // the caller's state into the engine's pinned staging slot for the next dqnx_agent_launch
 static int agent_pin_state(dqnx_engine* e, int32_t which, const uint32_t* state625) {
     if (!e->ag_rng_pin) {
@@ -4611,44 +4666,6 @@ int dqnx_agent_stage_rng(dqnx_engine* e, int32_t which, const uint32_t* state625
     rc = agent_pin_state(e, which, state625);
     if (rc) return rc;
     e->ag_expect_live = true;
-    return DQNX_OK;
-}
-
-static int agent_launch_impl(dqnx_engine* e, int32_t flags, void* stream, int* prev_rc);
-
-int dqnx_agent_learn_mt(dqnx_engine* e, uint32_t* mt, int32_t* pos, int32_t flags, void* stream, int64_t* words) {
-    if (!mt || !pos || !words) return set_error(DQNX_EINVAL, "bad argument");
-    if (*pos < 0 || *pos > 624) return set_error(DQNX_EINVAL, "MT position must be in [0, 624]");
-    uint32_t s625[625];
-    memcpy(s625, mt, 624 * 4);
-    s625[624] = (uint32_t)*pos;
-    int rc;
-    if (flags & DQNX_AGENT_LAUNCH) {
-        // the device only needs the state BEFORE the draw: stage it and launch first, then walk the draw
-        // on the host while the GPU runs the step (the walk of a 1024-row draw is ~7 us)
-        rc = check_bound(e);
-        if (rc) return rc;
-        if (e->pf_valid) return set_error(DQNX_ESTATE, "agent stage while a prefetched minibatch is pending");
-        if ((int64_t)e->Bs > e->ring_size) return set_error(DQNX_EINVAL, "Sample larger than population or is negative");
-        rc = agent_pin_state(e, DQNX_RNG_PY, s625);
-        if (rc) return rc;
-        e->ag_expect_live = false;   // (the check below is armed after the walk)
-        int prev_rc;
-        rc = agent_launch_impl(e, flags & ~DQNX_AGENT_LAUNCH, stream, &prev_rc);
-        if (rc) return rc;
-        rc = dqnx_rng_sample_words(s625, e->ring_size, e->Bs, e->ag_check, words);
-        if (rc) return rc;
-        e->ag_check_live = true;
-        e->ag_check_which = DQNX_RNG_PY;
-        memcpy(mt, e->ag_check, 624 * 4);   // the caller's generator moves past the draw
-        *pos = (int32_t)e->ag_check[624];
-        return prev_rc;   // the launched step's draw is mirrored; the previous step's checks raise
-    }
-    rc = dqnx_agent_stage_rng(e, DQNX_RNG_PY, s625, words);
-    if (rc) return rc;
-    // the caller's generator moves past the draw now (what random.sample would have consumed)
-    memcpy(mt, e->ag_expect, 624 * 4);
-    *pos = (int32_t)e->ag_expect[624];
     return DQNX_OK;
 }
 
@@ -4714,6 +4731,42 @@ static int agent_launch_impl(dqnx_engine* e, int32_t flags, void* stream, int* p
     memcpy(e->ag_check, e->ag_expect, sizeof(e->ag_check));
     e->ag_expect_live = false;
     e->ag_which = -1;
+    return DQNX_OK;
+}
+
+int dqnx_agent_learn_mt(dqnx_engine* e, uint32_t* mt, int32_t* pos, int32_t flags, void* stream, int64_t* words) {
+    if (!mt || !pos || !words) return set_error(DQNX_EINVAL, "bad argument");
+    if (*pos < 0 || *pos > 624) return set_error(DQNX_EINVAL, "MT position must be in [0, 624]");
+    uint32_t s625[625];
+    memcpy(s625, mt, 624 * 4);
+    s625[624] = (uint32_t)*pos;
+    int rc;
+    if (flags & DQNX_AGENT_LAUNCH) {
+        // the device only needs the state BEFORE the draw: stage it and launch first, then walk the draw
+        // on the host while the GPU runs the step (the walk of a 1024-row draw is ~7 us)
+        rc = check_bound(e);
+        if (rc) return rc;
+        if (e->pf_valid) return set_error(DQNX_ESTATE, "agent stage while a prefetched minibatch is pending");
+        if ((int64_t)e->Bs > e->ring_size) return set_error(DQNX_EINVAL, "Sample larger than population or is negative");
+        rc = agent_pin_state(e, DQNX_RNG_PY, s625);
+        if (rc) return rc;
+        e->ag_expect_live = false;   // (the check below is armed after the walk)
+        int prev_rc;
+        rc = agent_launch_impl(e, flags & ~DQNX_AGENT_LAUNCH, stream, &prev_rc);
+        if (rc) return rc;
+        rc = dqnx_rng_sample_words(s625, e->ring_size, e->Bs, e->ag_check, words);
+        if (rc) return rc;
+        e->ag_check_live = true;
+        e->ag_check_which = DQNX_RNG_PY;
+        memcpy(mt, e->ag_check, 624 * 4);   // the caller's generator moves past the draw
+        *pos = (int32_t)e->ag_check[624];
+        return prev_rc;   // the launched step's draw is mirrored; the previous step's checks raise
+    }
+    rc = dqnx_agent_stage_rng(e, DQNX_RNG_PY, s625, words);
+    if (rc) return rc;
+    // the caller's generator moves past the draw now (what random.sample would have consumed)
+    memcpy(mt, e->ag_expect, 624 * 4);
+    *pos = (int32_t)e->ag_expect[624];
     return DQNX_OK;
 }
 
