@@ -71,6 +71,12 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t wave_rsrc(const float* base, u
                                              __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
 
+// An input operand of an empty `asm volatile("" :: DQNX_KERNARG(a.x), ...)`: kernel arguments wanted
+// in SGPRs at that point.  The compiler otherwise loads each argument in the basic block that first
+// uses it, so a prologue with a few branches pays one dependent trip to the kernel-argument segment
+// per block; the operands of one such statement are loaded together, behind one wait.
+#define DQNX_KERNARG(x) "s"(x)
+
 // XCD-aware block remap (CDNA guide T1): blocks are dealt round-robin over the 8 XCDs, so
 // hand XCD x a CONTIGUOUS range of tiles (bijective for any total).  Speed only: placement
 // never affects results.

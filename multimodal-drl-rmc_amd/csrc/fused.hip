@@ -352,6 +352,26 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(fwd_waves<PH
     // LDS tile b: pointer arithmetic on `lds` keeps the LDS address space visible to the
     // compiler (ds_read, not flat loads that share the vmcnt counter with the W stream)
 #define FBUF(b) (lds + ((b) ? a.buf0 : 0))
+    // every argument the role branches, the tile mapping and the gather's loads read, in SGPRs here:
+    // their kernel-argument loads issue together behind one wait (DQNX_KERNARG, common.hpp)
+    if constexpr (PH == 2)
+        asm volatile("" ::DQNX_KERNARG(a.npc), DQNX_KERNARG(a.samp_shape), DQNX_KERNARG(a.tiles), DQNX_KERNARG(a.nstreams),
+                     DQNX_KERNARG(a.xcd_rows), DQNX_KERNARG(a.stream_of[0]), DQNX_KERNARG(a.stream_of[1]),
+                     DQNX_KERNARG(a.stream_of[2]), DQNX_KERNARG(a.Bl));
+    else if constexpr (BF)
+        asm volatile("" ::DQNX_KERNARG(a.npc), DQNX_KERNARG(a.samp_shape), DQNX_KERNARG(a.tiles), DQNX_KERNARG(a.nstreams),
+                     DQNX_KERNARG(a.xcd_rows), DQNX_KERNARG(a.stream_of[0]), DQNX_KERNARG(a.stream_of[1]),
+                     DQNX_KERNARG(a.stream_of[2]), DQNX_KERNARG(a.Bl), DQNX_KERNARG(a.in[0]), DQNX_KERNARG(a.out[0]),
+                     DQNX_KERNARG(a.adam_ctrl), DQNX_KERNARG(a.phys), DQNX_KERNARG(a.qp_magic), DQNX_KERNARG(a.wblk[0][0]),
+                     DQNX_KERNARG(a.wblk[1][0]), DQNX_KERNARG(a.ring16_obs), DQNX_KERNARG(a.ring16_next),
+                     DQNX_KERNARG(a.stride16));
+    else
+        asm volatile("" ::DQNX_KERNARG(a.npc), DQNX_KERNARG(a.samp_shape), DQNX_KERNARG(a.tiles), DQNX_KERNARG(a.nstreams),
+                     DQNX_KERNARG(a.xcd_rows), DQNX_KERNARG(a.stream_of[0]), DQNX_KERNARG(a.stream_of[1]),
+                     DQNX_KERNARG(a.stream_of[2]), DQNX_KERNARG(a.Bl), DQNX_KERNARG(a.in[0]), DQNX_KERNARG(a.out[0]),
+                     DQNX_KERNARG(a.adam_ctrl), DQNX_KERNARG(a.phys), DQNX_KERNARG(a.qp_magic), DQNX_KERNARG(a.wblk[0][0]),
+                     DQNX_KERNARG(a.wblk[1][0]), DQNX_KERNARG(a.ring_obs), DQNX_KERNARG(a.ring_next),
+                     DQNX_KERNARG(a.ring_stride));
     if (a.npc && blockIdx.x == 0) {   // PER: the next sample's numpy MT blocks, twisted ahead on their own CU
         np_cache_extend(a.npc, a.np_state, a.npc_blocks, reinterpret_cast<uint32_t*>(lds));
         return;
@@ -380,19 +400,21 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(fwd_waves<PH
     const int bid = (int)blockIdx.x - ((a.samp_shape || a.npc) ? 1 : 0);
     const int T0 = xcd_remap(bid, a.tiles * a.nstreams * nsp);
     int part = T0 % nsp, T = T0 / nsp;   // the parts of one row tile are neighbours (one XCD)
-    int z = T / a.tiles, tile = T - z * a.tiles;
+    // the grid slice z = T / tiles by comparison (at most 3 streams), not a runtime division
+    int z = (T >= a.tiles ? 1 : 0) + (T >= 2 * a.tiles ? 1 : 0), tile = T - z * a.tiles;
     if constexpr (PH == 3) {   // the two parts of a row tile: blocks bid and bid ^ 8 (one XCD, tiles % 8 == 0)
         const int tp = a.tiles >> 3, L = bid >> 3, L2 = L >> 1;
         part = L & 1;
-        z = L2 / tp;
+        z = (L2 >= tp ? 1 : 0) + (L2 >= 2 * tp ? 1 : 0);
         tile = (L2 - z * tp) * 8 + (bid & 7);
     } else if (PH != 1 && a.xcd_rows) {   // row tile t of every stream on XCD t % 8 (tiles % 8 == 0)
         const int tp = a.tiles >> 3, L = bid >> 3;
-        z = L / tp;
+        z = (L >= tp ? 1 : 0) + (L >= 2 * tp ? 1 : 0);
         tile = (L - z * tp) * 8 + (bid & 7);
         part = 0;
     }
-    const int s = a.stream_of[z];
+    // (selected from the pinned arguments: a.stream_of[z] would be a dependent load ahead of the gather)
+    const int s = z == 0 ? a.stream_of[0] : (z == 1 ? a.stream_of[1] : a.stream_of[2]);
     const int tgt = s == 2 ? 1 : 0;
     const int b0 = tile * RW, nb = min(RW, a.Bl - b0);
     const float* P = tgt ? a.tparams : a.params;
@@ -451,10 +473,19 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(fwd_waves<PH
         // branch-free: every slot loads (clamped row / column) and selects zero afterwards,
         // so the loads issue back to back (one phys round trip, then one ring round trip)
         if (DQNX_FUSED_ORDER == 1) stream_open<MTN>(a.wblk[tgt][0], a.out[0] >> 4, fwd_nch<BF>(a.in[0]), coff >> 4, c, ws, wb, tile);
+        // each slot's (row, piece), derived once for the three passes below: q / qp as a multiply-high
+        // by the host's ceil(2^32 / qp) (exact while q * qp < 2^32; q < FGQ * FT, qp <= 192)
+        int gr[GQ], gc[GQ];
+#pragma unroll
+        for (int j = 0; j < GQ; j++) {
+            const int q = tid + j * FT;
+            gr[j] = (int)__umulhi((uint32_t)q, a.qp_magic);
+            gc[j] = q - gr[j] * qp;
+        }
         int32_t slot[GQ];
 #pragma unroll
         for (int j = 0; j < GQ; j++) {
-            const int r = (tid + j * FT) / qp;
+            const int r = gr[j];
             slot[j] = a.phys[b0 + (r < nb ? r : nb - 1)];
         }
         // stream 0 also gathers the transition scalars for the head kernel (one contiguous
@@ -467,8 +498,7 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(fwd_waves<PH
         const uint16_t* ring16 = BF ? ((s == 0) ? a.ring16_obs : a.ring16_next) : nullptr;
 #pragma unroll
         for (int j = 0; j < GQ; j++) {
-            const int q = tid + j * FT;
-            const int r = q / qp, cp = q - r * qp;
+            const int r = gr[j], cp = gc[j];
             const bool ok = r < nb && cp < rsp;
             u32x4 x;
             if constexpr (BF)
@@ -484,8 +514,7 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(fwd_waves<PH
             a.trans[b0 + tid] = make_float4(__int_as_float(a.act[tslot]), a.rew[tslot], a.done[tslot], 0.f);
 #pragma unroll
         for (int j = 0; j < GQ; j++) {
-            const int q = tid + j * FT;
-            const int r = q / qp, cp = q - r * qp;
+            const int r = gr[j], cp = gc[j];
             if (r < RW) {
                 if constexpr (BF) {
                     *reinterpret_cast<u32x4*>(reinterpret_cast<uint16_t*>(FBUF(0)) + r * a.sx + 8 * cp) = xv[j];
@@ -701,12 +730,19 @@ __global__ __launch_bounds__(FT) void k_head_bwd(HeadBwdArgs a) {
     const int i = lane & 15, g = lane >> 4;
     // nsplit workgroups per 16-sample tile: each recomputes the (cheap) head part and takes
     // 1/nsplit of the columns of the LAST dZ of the chain (dZ_1, the widest)
-    int tile = blockIdx.x / a.nsplit, part = blockIdx.x - tile * a.nsplit;
+    // every argument the tile mapping and the prologue loads read: one wait (DQNX_KERNARG, common.hpp)
+    asm volatile("" ::DQNX_KERNARG(a.nsplit), DQNX_KERNARG(a.xcd_rows), DQNX_KERNARG(a.xcd_shift), DQNX_KERNARG(a.xcd_mr),
+                 DQNX_KERNARG(a.Bl), DQNX_KERNARG(a.NH), DQNX_KERNARG(a.F), DQNX_KERNARG(a.head_kind), DQNX_KERNARG(a.params),
+                 DQNX_KERNARG(a.head_off), DQNX_KERNARG(a.raw), DQNX_KERNARG(a.trans), DQNX_KERNARG(a.isw),
+                 DQNX_KERNARG(a.H[NL - 1]));
+    // nsplit and xcd_mr are 1, 2 or 4 (launch_head_bwd checks): shifts, not runtime divisions
+    const int nsh = __builtin_ctz(a.nsplit), msh = __builtin_ctz(a.xcd_mr);
+    int tile = (int)(blockIdx.x >> nsh), part = blockIdx.x - (tile << nsh);
     if (a.xcd_rows) {   // tile t on the XCD whose L2 holds the forward's outputs of its row tile t / xcd_mr
         const int xh = blockIdx.x & 7, k = blockIdx.x >> 3;
-        const int kt = k / a.nsplit, mr = a.xcd_mr;
-        tile = ((kt / mr) * 8 + ((xh - a.xcd_shift) & 7)) * mr + (kt - (kt / mr) * mr);
-        part = k - kt * a.nsplit;
+        const int kt = k >> nsh;
+        tile = ((((kt >> msh) * 8 + ((xh - a.xcd_shift) & 7))) << msh) + (kt - ((kt >> msh) << msh));
+        part = k - (kt << nsh);
     }
     const bool lead = part == 0;
     const int b0 = tile * 16, nb = min(16, a.Bl - b0);
@@ -724,8 +760,7 @@ __global__ __launch_bounds__(FT) void k_head_bwd(HeadBwdArgs a) {
     int coff = 0, ldn = 0;
     auto setup = [&](int l) {
         const int K = a.out[l], N = a.in[l];
-        const int nparts = (l == 1) ? a.nsplit : 1;
-        const int np_ = N / nparts;
+        const int np_ = (l == 1) ? N >> nsh : N;
         coff = (l == 1) ? part * np_ : 0;
         ldn = N;
         cw = wave_cols(np_);
@@ -1348,6 +1383,9 @@ int launch_dw_bf16(const BwdArgs& a, hipStream_t s) {
 }
 
 // ---- host side ------------------------------------------------------------------------
+// ceil(2^32 / qp) for the gather's row-of-piece multiply-high (qp >= 4: whole 16- or 32-column chunks)
+static uint32_t fwd_qp_magic(int qp) { return (uint32_t)(((1ull << 32) + (uint64_t)qp - 1) / (uint64_t)qp); }
+
 bool fused_fwd_plan(FusedFwdArgs& a, int obs_dim, bool bf16, int mr) {
     if (mr != 1 && mr != 2 && mr != 4) return false;
     if (a.L < 1 || a.L > FUSED_MAX_L || a.NH > 16) return false;
@@ -1358,6 +1396,7 @@ bool fused_fwd_plan(FusedFwdArgs& a, int obs_dim, bool bf16, int mr) {
     const int kz = bf16 ? fwd_nch<true>(obs_dim) * 32 : fwd_nch<false>(obs_dim) * 16;
     if (16 * (kz / 4) > FGQ * FT) return false;   // gather slots (per 16 rows)
     a.gw = kz / 4 <= FWD_NARROW_Q4 ? 0 : 1;
+    a.qp_magic = fwd_qp_magic(kz / (bf16 ? 8 : 4));
     if (a.gw && mr != 1) return false;   // wide rows: 16-row tiles only
     const int rw = 16 * mr;
     a.mr = mr;
@@ -1410,6 +1449,8 @@ int launch_fused_fwd(const FusedFwdArgs& a, int act, hipStream_t s) {
     if (a.phase == 3 && !pair_ok)
         return set_error(DQNX_EUNSUPPORTED, "paired forward: fp32, L >= 2, 16-row tiles, tiles %% 8 == 0, layer 1 width a "
                                             "multiple of 32 and <= %d, later layers <= %d wide", 32 * FW, 16 * FW);
+    if (a.phase != 2 && a.qp_magic != fwd_qp_magic((a.bf16 ? fwd_nch<true>(a.in[0]) * 32 : fwd_nch<false>(a.in[0]) * 16) / (a.bf16 ? 8 : 4)))
+        return set_error(DQNX_EINVAL, "fused forward: the gather's row divisor was not planned for %d input columns", a.in[0]);
     if (a.gw && (a.phase != 0 || a.mr != 1))
         return set_error(DQNX_EUNSUPPORTED, "fused forward: rows wider than %d columns take the one-launch 16-row plan", 4 * FWD_NARROW_Q4);
     if (a.samp_shape && (a.phase == 2 || a.samp_shape > 3 || a.samp.k > FWD_SAMPLE_MAX_K ||
@@ -1474,6 +1515,9 @@ int launch_fused_fwd(const FusedFwdArgs& a, int act, hipStream_t s) {
 
 int launch_head_bwd(const HeadBwdArgs& a, int act, hipStream_t s) {
     const dim3 grid(((a.Bl + 15) / 16) * a.nsplit), block(FT);
+    auto pow2_le4 = [](int v) { return v == 1 || v == 2 || v == 4; };
+    if (!pow2_le4(a.nsplit) || !pow2_le4(a.xcd_mr))   // (the kernel divides by them with shifts)
+        return set_error(DQNX_EINVAL, "fused head: nsplit %d / row-tile height %d must be 1, 2 or 4", a.nsplit, a.xcd_mr);
     const size_t pad = DQNX_HEAD_LDS_PAD;   // dynamic LDS on top of the static tiles (occupancy knob)
 #define HEAD_BWD_CASE(ACTV, NLV)                                                                     \
     do {                                                                                             \

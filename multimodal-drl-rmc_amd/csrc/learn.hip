@@ -1117,6 +1117,12 @@ __global__ __launch_bounds__(64 * DW16_NW) void k_dw_adam16(DwAdam16Args a) {
     __shared__ float redb[DW16_NW][R][64];
     const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 15, g = lane >> 4;
+    // the arguments of the role branch and the tile -> layer mapping behind one wait (DQNX_KERNARG,
+    // common.hpp): the layer record is then the second scalar trip
+    static_assert(DQNX_MAX_DENSE == 6, "the first-tile operands below");
+    asm volatile("" ::DQNX_KERNARG(a.tiles), DQNX_KERNARG(a.nl), DQNX_KERNARG(a.mode), DQNX_KERNARG(a.soft),
+                 DQNX_KERNARG(a.L[1].t0), DQNX_KERNARG(a.L[2].t0), DQNX_KERNARG(a.L[3].t0), DQNX_KERNARG(a.L[4].t0),
+                 DQNX_KERNARG(a.L[5].t0), DQNX_KERNARG(a.L[6].t0));
     if ((int)blockIdx.x >= a.tiles) {   // extra workgroups: PER tracking, sampler cache, the staged-minibatch copy, PER prop
         const int x = (int)blockIdx.x - a.tiles - a.ptrack - (a.mtc ? 1 : 0) - (a.pf_nidx > 0 ? 1 : 0);
         if (x >= 0) {   // k_per_prop's body over 64 * DW16_NW updates (the red table as its LDS)
@@ -1140,6 +1146,10 @@ __global__ __launch_bounds__(64 * DW16_NW) void k_dw_adam16(DwAdam16Args a) {
             for (int q = tid; q < a.pf_nidx; q += blockDim.x) a.pf_idx_dst[q] = a.pf_idx_src[q];
             for (int q = tid; q < a.pf_nphys; q += blockDim.x) a.pf_phys_dst[q] = a.pf_phys_src[q];
         }
+        // vmcnt(0): the compiler joins this return with the tiles' path below, and its wait counts
+        // then take these roles' loads for outstanding there (a full drain ahead of the K loop's
+        // first loads, behind the parameter loads meant to hide under that loop)
+        __builtin_amdgcn_s_waitcnt(0x0f70);
         return;
     }
     DQNX_STAMP(a.stamps, 56);

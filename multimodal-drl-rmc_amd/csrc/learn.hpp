@@ -488,6 +488,7 @@ struct FusedFwdArgs {
     const float* ring_obs;
     const float* ring_next;
     int ring_stride;             // floats per ring row (obs_dim rounded up to 4)
+    uint32_t qp_magic;           // ceil(2^32 / gather pieces per row): piece q's row is umulhi(q, qp_magic)
     // bf16 compute: the rows as bf16 copies (RNE of the fp32 rows, written by the replay push), which is
     // all the bf16 GEMMs read of them; the forward gathers these (half the bytes), bitwise the same operands
     const uint16_t* ring16_obs;
