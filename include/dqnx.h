@@ -63,6 +63,7 @@ enum dqnx_algo { DQNX_ALGO_DQN = 0, DQNX_ALGO_DOUBLE = 1, DQNX_ALGO_PER_DOUBLE =
  *             fc_val/fc_adv + aggregate (R:dqn/network.py:77-96). */
 #define DQNX_MAX_DENSE 6
 #define DQNX_MAX_CONV 4
+#define DQNX_NSTEP_MAX 16      /* largest dqnx_config.n_step */
 typedef struct dqnx_net_desc {
     int32_t kind;              /* dqnx_net_kind */
     int32_t head;              /* dqnx_head_kind */
@@ -102,6 +103,11 @@ typedef struct dqnx_config {
     int32_t batch;             /* global minibatch = batch_size (k of random.sample) */
     int32_t world_size;        /* data-parallel ranks (1 = single GPU) */
     int32_t rank;              /* this rank: processes samples [rank*batch/world, (rank+1)*batch/world) */
+    int32_t n_step;            /* n-step returns: 1 (dqnx_config_defaults) .. DQNX_NSTEP_MAX; fixed at create, sizes
+                                  the arena, never in the state blob ("n-step returns" below).  It lies in the
+                                  four bytes that were padding in front of `capacity`: the struct's size and
+                                  every other field's offset are what they were, and dqnx_config_defaults
+                                  (which every caller fills the struct through) has always written them */
     int64_t capacity;          /* buffer_size (deque maxlen / SumTree capacity) */
     /* hyper-parameters are doubles, like the reference's Python floats; the engine casts
      * them to fp32 exactly where torch does (tensor * Python float). */
@@ -155,6 +161,9 @@ typedef struct dqnx_ctrl {
 #define DQNX_DEVERR_BOUNDS_ADAM_WIDE 16  /*   k_adam4 wide path: a float4 outside [e0, n_params) of the launch */
 #define DQNX_DEVERR_BOUNDS_ADAM_PERM 17  /*   k_adam4 wide path: a permuted conv-weight copy outside the range */
 #define DQNX_DEVERR_BOUNDS_MICRO_DW 18   /*   k_micro_dw: a split-K slab tile outside its conv's slabs */
+/* n-step engines: the gather launch met a ring size / write pointer / sampled slot outside the ring (the row
+ * then reads a one-position window at a clamped slot: every access stays inside the ring) */
+#define DQNX_DEVERR_NSTEP_STATE 19
 
 /* ---- engine lifetime --------------------------------------------------------------- */
 typedef struct dqnx_engine dqnx_engine;
@@ -219,7 +228,11 @@ int dqnx_engine_set_graphs(dqnx_engine* e, int32_t enabled);
  * with one async copy -- the caller's arrays are free on return; larger pushes are copied with
  * hipMemcpyAsync and the call synchronises the stream) or device memory (src_on_device = 1).  obs rows are
  * obs_dim floats, contiguous.  done: 0/1 bytes.  Under PER new leaves get the current
- * max priority (1.0 when the tree is empty), exactly as the reference. */
+ * max priority (1.0 when the tree is empty), exactly as the reference.
+ * Row order: time-major, env-minor -- one time step is n_env consecutive rows, env 0 first (what
+ * Agent.store_transitions hands over).  An n-step engine (n_step > 1) relies on it: the successor of a row
+ * is the row n_env later, so there a push whose n is not a multiple of n_env returns DQNX_EINVAL (nothing
+ * is written). */
 int dqnx_replay_push(dqnx_engine* e, const float* obs, const int32_t* act, const float* rew,
                      const uint8_t* done, const float* next_obs, int32_t n, int32_t src_on_device,
                      void* stream);
@@ -637,6 +650,65 @@ typedef struct dqnx_grad_clip_info {
     float last_norm, last_coef;
 } dqnx_grad_clip_info;
 int dqnx_grad_clip_info_get(dqnx_engine* e, dqnx_grad_clip_info* out_host, int32_t reset, void* stream);
+
+/* ---- n-step returns: multi-step TD targets for every learn route, gathered on the device ----
+ * dqnx_config.n_step = n in 1 .. DQNX_NSTEP_MAX (anything else: DQNX_EINVAL at create).  The replay ring
+ * stays the 1-step ring the reference fills (R:dqn/replay_memory.py:30-36): a push of n_env rows is one
+ * time step, so the successor of logical position p (0 = oldest) in the same environment is p + n_env, and
+ * the n-step transition of a sampled start row p is assembled at sample time from the ring as it is.  With
+ * size = dqnx_ctrl.ring_size, gamma = cfg.gamma (a double) and n_env = cfg.n_env:
+ *
+ *   g = 1.0; R = 0.0; m = 0; d = 0.0                  (fp64)
+ *   for j in 0 .. n-1:
+ *       q = p + j*n_env
+ *       if q >= size: break                            the window reaches the newest end of the ring
+ *       R += g * (double)rew[q]                        one fp64 multiply, one fp64 add, no contraction
+ *       g *= gamma                                     repeated multiply, not pow
+ *       m = j + 1
+ *       if done[q] != 0: d = 1.0; break
+ *   last = p + (m-1)*n_env
+ *   row  = ( obs[p], act[p], (float)R, d, next_obs[last] ),  disc = (float)g = fp32(gamma^m)
+ *   y    = R + ((1 - d) * disc) * q'                   the head's fp32 order, disc where (float)gamma stands
+ *
+ * m >= 1 always; n = 1 gives R = rew[p], d = done[p], last = p, disc = (float)gamma: the default step bit
+ * for bit.  Sampling is unchanged (the draw and its RNG consumption stay bit-exact), a SumTree leaf still
+ * means one ring slot, and PER priorities attach to the start row p (a sampled ring slot maps to its
+ * logical position by (slot - (ring_wptr - ring_size)) mod capacity).  The state blob does not change: a
+ * blob saved by an n-step engine loads into a 1-step engine and the other way round.
+ *
+ * Launches: an n-step engine's learn step gains ONE launch, "nstep_gather", its first compute launch: it
+ * follows the launch that makes the step's slot table final (the sampler "sample_uniform" / "per_sample" /
+ * "idx_to_phys"; in the steady state of a prefetching loop, where the previous step left the minibatch,
+ * it is the step's first launch).  For each of the batch_local rows it walks the window and writes the
+ * materialised minibatch: the last part of DQNX_BUF_WORKSPACE of an n-step engine (a default engine's
+ * workspace has no such part: dqnx_nstep_buffer reports 0 bytes), rewritten by every learn step, never in
+ * the state blob.  Its sub-arrays follow each other from the offset dqnx_nstep_buffer gives, in this order,
+ * each at the next multiple of 256 bytes (Bl = batch / world_size, S = dqnx_engine_obs_stride):
+ *   mb_obs [Bl][S] fp32, mb_next [Bl][S] fp32 (the row of slot `last`), mb_act [Bl] int32, mb_rew [Bl] fp32,
+ *   mb_done [Bl] fp32, mb_disc [Bl] fp32, mb_phys [Bl] int32 (the identity: mb_phys[b] = b),
+ *   mb_start [Bl] {int32 act, fp32 rew, fp32 done, 0} of the START rows, then (DQNX_COMPUTE_BF16 engines) the
+ *   bf16 copies of mb_obs and mb_next, [Bl][S16] each, S16 = obs_dim rounded up to a multiple of 8.
+ * Every other launch of the step reads these where a default engine reads the ring through its slot table;
+ * no forward, backward or Adam kernel differs, and the two head kernels multiply by mb_disc[b] where they
+ * multiply by (float)gamma.  dqnx_learn_kernel_count / _info / dqnx_learn_step_timed / _omit list the launch
+ * (0 FLOPs; bytes = the rows and scalars moved).  An engine with n_step = 1 launches exactly what it launched
+ * before this section and has the same arena size; DQNX_NSTEP_FORCE=1 in the environment at create sends it through the
+ * gather too (for testing the route: bitwise the default).
+ * Composition: every step flag and entry point works as before -- PER, bf16, gradient clipping,
+ * DQNX_STEP_PREFETCH, dqnx_learn_steps, graphs, DQNX_STEP_GRADS_ONLY + dqnx_apply_grads (world_size > 1: each
+ * rank gathers its own shard's rows), the bucketed step, the agent fast path.  The only new refusal is
+ * dqnx_replay_push's row-count rule above.
+ * DQNX_STEP_STATS: reward_sum, done_rows and taken_hist describe the sampled START rows (mb_start: the 1-step
+ * reward and done of row p); target_*, abs_td_*, td_hist and huber_linear_rows describe the n-step target.
+ *
+ * dqnx_nstep_window (test hook, host only, no engine, no GPU): the window of start position p over rew /
+ * done arrays indexed by logical position, by the same inline function the gather kernel calls.  DQNX_EINVAL
+ * unless 0 <= p < size, 1 <= n_step <= DQNX_NSTEP_MAX and n_env >= 1.  Any output pointer may be NULL. */
+/* Arena offset and size of the materialised minibatch (host only; *bytes = 0 for a default engine). */
+int dqnx_nstep_buffer(const dqnx_engine* e, uint64_t* offset, uint64_t* bytes);
+int dqnx_nstep_window(const float* rew, const float* done, int64_t size, int64_t p, int32_t n_step,
+                      int32_t n_env, double gamma, float* R, float* d, float* disc,
+                      int64_t* last, int32_t* m);
 
 /* ---- kernel-level timing (bench.py roofline) ---------------------------------------
  * A learn step is an ordered list of kernel launches (sample, linear_fwd_l1.., head_td_loss,

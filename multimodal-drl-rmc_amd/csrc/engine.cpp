@@ -14,10 +14,12 @@
 #include <map>
 #include <memory>
 #include <tuple>
+#include <type_traits>
 #include <string>
 #include <vector>
 
 #include "learn.hpp"
+#include "nstep.hpp"
 
 namespace dqnx {
 
@@ -450,6 +452,14 @@ struct dqnx_engine {
     double grad_clip = 0.0;
     int64_t clip_chunk = 0;
     int clip_parts = 0;
+    // n-step returns (nstep.hip): the engine's steps read a minibatch materialised by "nstep_gather"
+    // (cfg.n_step > 1, or DQNX_NSTEP_FORCE=1 at create); its sub-arrays, the workspace's last part
+    bool nstep = false;
+    // its workgroups follow the fused forward's row-tile XCDs (DQNX_NSTEP_XCD at create: 0 = launch order,
+    // 2 = four XCDs away from the forward's, the worst placement, for measuring what the rule is worth)
+    int nstep_xcd = 1;
+    uint64_t nb_obs = 0, nb_next = 0, nb_act = 0, nb_rew = 0, nb_done = 0, nb_disc = 0, nb_phys = 0, nb_start = 0;
+    uint64_t nb_obs16 = 0, nb_next16 = 0, nb_bytes = 0;
     char* arena = nullptr;
     int64_t ring_size = 0, ring_wptr = 0;   // host mirror of the ring state (pushes are host-driven)
     bool graphs = false;   // eager launches by default (dqnx_engine_set_graphs)
@@ -670,6 +680,24 @@ int layout(dqnx_engine* e) {
     }
     e->ws_stats_part = sub(stats_part_bytes(e->stats_bwg, e->stats_chunks));
     e->ws_stats_ticket = sub(64);
+    // n-step engines only: the materialised minibatch, the workspace's last part (include/dqnx.h "n-step
+    // returns" fixes the order).  A default engine's workspace, and so its arena, is what it was without it.
+    if (e->nstep) {
+        const uint64_t Bl = (uint64_t)e->Bl;
+        e->nb_obs = sub(Bl * e->stride * 4);
+        e->nb_next = sub(Bl * e->stride * 4);
+        e->nb_act = sub(Bl * 4);
+        e->nb_rew = sub(Bl * 4);
+        e->nb_done = sub(Bl * 4);
+        e->nb_disc = sub(Bl * 4);
+        e->nb_phys = sub(Bl * 4);
+        e->nb_start = sub(Bl * 16);
+        if (e->stride16) {
+            e->nb_obs16 = sub(Bl * e->stride16 * 2);
+            e->nb_next16 = sub(Bl * e->stride16 * 2);
+        }
+        e->nb_bytes = cur - e->nb_obs;
+    }
     cur = align_up(cur, 256);
     e->bytes[DQNX_BUF_WORKSPACE] = cur - e->off[DQNX_BUF_WORKSPACE];
     region(DQNX_BUF_LEARN_STATS, sizeof(dqnx_learn_stats));   // after the workspace: every earlier offset stays
@@ -999,10 +1027,61 @@ static bool per_track_inlaunch(const dqnx_engine* e, int flags) {
     return per_fused_update(e, flags) && route_knob("DQNX_PER_TRACK_INLAUNCH", 1) != 0;
 }
 
+// Where a step's launches gather their rows and read the transition scalars: the replay ring through
+// the step's slot table `phys`, or (n-step engine) the minibatch "nstep_gather" materialised from it,
+// through the identity table (include/dqnx.h "n-step returns").
+struct RowSource {
+    const int32_t* phys;
+    const float *obs, *next;
+    const uint16_t *obs16, *next16;   // bf16 engines (stride16 != 0), else null
+    const int32_t* act;
+    const float *rew, *done;
+    const float* disc;                // per-row discount of an n-step engine, or null: (float)gamma
+};
+
+RowSource row_source(dqnx_engine* e, const int32_t* phys) {
+    RowSource rs;
+    if (e->nstep) {
+        rs.phys = at<int32_t>(e, e->nb_phys);
+        rs.obs = at<float>(e, e->nb_obs);
+        rs.next = at<float>(e, e->nb_next);
+        rs.obs16 = e->stride16 ? at<uint16_t>(e, e->nb_obs16) : nullptr;
+        rs.next16 = e->stride16 ? at<uint16_t>(e, e->nb_next16) : nullptr;
+        rs.act = at<int32_t>(e, e->nb_act);
+        rs.rew = at<float>(e, e->nb_rew);
+        rs.done = at<float>(e, e->nb_done);
+        rs.disc = at<float>(e, e->nb_disc);
+        return rs;
+    }
+    rs.phys = phys;
+    rs.obs = at<float>(e, e->off[DQNX_BUF_RING_OBS]);
+    rs.next = at<float>(e, e->off[DQNX_BUF_RING_NEXT_OBS]);
+    rs.obs16 = e->stride16 ? at<uint16_t>(e, e->ws_ring16[0]) : nullptr;
+    rs.next16 = e->stride16 ? at<uint16_t>(e, e->ws_ring16[1]) : nullptr;
+    rs.act = at<int32_t>(e, e->off[DQNX_BUF_RING_ACT]);
+    rs.rew = at<float>(e, e->off[DQNX_BUF_RING_REW]);
+    rs.done = at<float>(e, e->off[DQNX_BUF_RING_DONE]);
+    rs.disc = nullptr;
+    return rs;
+}
+
+// the fused plan's row tile t of every stream (and the head's tile t) on XCD t % 8 (build_fused_steps)
+bool fused_xcd_rows(const dqnx_engine* e) {
+    const int ftiles = (e->Bl + 15) / 16;
+    const int frows = 16 * e->fplan.mr;
+    return route_knob("DQNX_XCD_ROWS", 1) != 0 && ftiles % 8 == 0 &&
+           (e->fplan.mr == 1 || (route_knob("DQNX_XCD_ROWS_MR", 1) != 0 && e->Bl % frows == 0 &&
+                                 (e->Bl / frows) % 8 == 0));
+}
+// ... whose workgroups the forward's extra block 0 (the sampler of the next step, the numpy MT cache) shifts by one
+bool fused_xcd_shift(const dqnx_engine* e, bool sample_next) {
+    return sample_next || (e->ws_npc && e->cfg.algo == DQNX_ALGO_PER_DOUBLE);
+}
+
 // Fused MLP plan (bwd_plan 2): forward of every layer + head in one launch, head / TD /
 // dZ chain in one launch, every dW in one split-K launch, then the Adam pass.
-void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, std::vector<KStep>& ks,
-                       const SampleArgs* sample_next) {
+void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, const RowSource& rs,
+                       std::vector<KStep>& ks, const SampleArgs* sample_next) {
     const dqnx_config& c = e->cfg;
     const NetPlan& np = e->np;
     const int L = (int)np.dense.size();
@@ -1022,12 +1101,8 @@ void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, s
     // row tile t of every stream (and the head's tile t) on XCD t % 8: the head kernel then reads
     // the forward's outputs from its own XCD's L2 (16-row tiles, tiles % 8 == 0).  Measured at
     // B=1024: head_bwd 7.2 -> 6.6 us, the forward unchanged; DQNX_XCD_ROWS=0 keeps xcd_remap's order
-    const int ftiles = (e->Bl + 15) / 16;
     // (row tiles of 16 * mr rows: the head kernel's 16-sample tiles follow their row tile's XCD)
-    const int frows = 16 * e->fplan.mr;
-    const bool xcd_rows = route_knob("DQNX_XCD_ROWS", 1) != 0 && ftiles % 8 == 0 &&
-                          (e->fplan.mr == 1 || (route_knob("DQNX_XCD_ROWS_MR", 1) != 0 && e->Bl % frows == 0 &&
-                                                (e->Bl / frows) % 8 == 0));
+    const bool xcd_rows = fused_xcd_rows(e);
     // 2. forward (R:dqn/agent.py:209-214 / 172-173 streams, R:dqn/network.py:61-65, 90-96)
     {
         FusedFwdArgs fa = e->fplan;
@@ -1042,13 +1117,13 @@ void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, s
         fa.stream_of[2] = 2;
         fa.params = params;
         fa.tparams = tparams;
-        fa.ring_obs = at<float>(e, e->off[DQNX_BUF_RING_OBS]);
-        fa.ring_next = at<float>(e, e->off[DQNX_BUF_RING_NEXT_OBS]);
+        fa.ring_obs = rs.obs;
+        fa.ring_next = rs.next;
         fa.ring_stride = e->stride;
-        fa.ring16_obs = e->stride16 ? at<uint16_t>(e, e->ws_ring16[0]) : nullptr;
-        fa.ring16_next = e->stride16 ? at<uint16_t>(e, e->ws_ring16[1]) : nullptr;
+        fa.ring16_obs = rs.obs16;
+        fa.ring16_next = rs.next16;
         fa.stride16 = e->stride16;
-        fa.phys = phys;
+        fa.phys = rs.phys;
         fa.xcopy = at<float>(e, e->ws_xobs);
         for (int l = 0; l < L; l++) fa.H[l] = at<float>(e, e->ws_H[l]);   // stream-0 third of [3][Bl][w]
         if (e->dwt) {   // + the T16 copies k_dw_bf16t reads
@@ -1058,9 +1133,9 @@ void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, s
         }
         fa.raw = at<float>(e, e->ws_raw);
         fa.trans = at<float4>(e, e->ws_trans);
-        fa.act = at<int32_t>(e, e->off[DQNX_BUF_RING_ACT]);
-        fa.rew = at<float>(e, e->off[DQNX_BUF_RING_REW]);
-        fa.done = at<float>(e, e->off[DQNX_BUF_RING_DONE]);
+        fa.act = rs.act;
+        fa.rew = rs.rew;
+        fa.done = rs.done;
         for (int l = 0; l < L; l++) {
             fa.wblk[0][l] = at<float>(e, e->ws_wblk[0][l]);
             fa.wblk[1][l] = at<float>(e, e->ws_wblk[1][l]);
@@ -1178,13 +1253,14 @@ void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, s
         ha.head_off = np.head_off;
         ha.inv_bg = (float)(1.0 / (double)e->Bg);
         ha.gamma = (float)c.gamma;
+        ha.disc = rs.disc;
         ha.params = params;
         ha.raw = at<float>(e, e->ws_raw);
         ha.trans = at<float4>(e, e->ws_trans);
-        ha.phys = phys;
-        ha.act = at<int32_t>(e, e->off[DQNX_BUF_RING_ACT]);
-        ha.rew = at<float>(e, e->off[DQNX_BUF_RING_REW]);
-        ha.done = at<float>(e, e->off[DQNX_BUF_RING_DONE]);
+        ha.phys = rs.phys;
+        ha.act = rs.act;
+        ha.rew = rs.rew;
+        ha.done = rs.done;
         ha.isw = (c.algo == DQNX_ALGO_PER_DOUBLE) ? at<float>(e, e->off[DQNX_BUF_IS_WEIGHTS]) + e->shard_begin : nullptr;
         ha.abs_td_out = (c.algo == DQNX_ALGO_PER_DOUBLE) ? at<float>(e, e->off[DQNX_BUF_PER_ABS_TD]) + e->shard_begin
                                                          : nullptr;
@@ -1200,7 +1276,7 @@ void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, s
         ha.ctrl = nullptr;   // the forward launch stores the step's Adam scalars
         ha.xcd_rows = xcd_rows ? 1 : 0;
         ha.xcd_mr = e->fplan.mr;
-        ha.xcd_shift = (sample_next || (e->ws_npc && c.algo == DQNX_ALGO_PER_DOUBLE)) ? 1 : 0;   // forward's block 0
+        ha.xcd_shift = fused_xcd_shift(e, sample_next != nullptr) ? 1 : 0;   // forward's block 0
         for (int l = 1; l < L; l++) ha.wblkT[l] = at<float>(e, e->ws_wblkT[l]);
         ha.ab = adam_bias_args(e);
         ha.stamps = at<int64_t>(e, e->ws_stamps);
@@ -1565,7 +1641,12 @@ static KStep stats_kstep(dqnx_engine* e, int key) {
     sa.q = at<float>(e, e->off[DQNX_BUF_Q]);
     sa.td = at<float>(e, e->off[DQNX_BUF_TD]);
     sa.isw = c.algo == DQNX_ALGO_PER_DOUBLE ? at<float>(e, e->off[DQNX_BUF_IS_WEIGHTS]) : nullptr;
-    if (e->bwd_plan == 2) {
+    if (e->nstep) {
+        // n-step engine: reward_sum / done_rows / taken_hist describe the sampled START rows, whose ring
+        // scalars "nstep_gather" kept (the TD fields describe the n-step target); still this step's when
+        // the step's last compute launch has already copied the next minibatch over the index slot
+        sa.trans = at<float4>(e, e->nb_start);
+    } else if (e->bwd_plan == 2) {
         sa.trans = at<float4>(e, e->ws_trans);
     } else {
         sa.phys = at<int32_t>(e, e->ws_phys) + (size_t)slot * e->Bl;
@@ -1608,7 +1689,11 @@ struct StepCtx {
     int key, flags, slot;
     int32_t *idx, *phys;
     float *params, *tparams;
+    // the rows the step's launches gather (RowSource): the ring through `phys`, or an n-step engine's
+    // materialised minibatch; ring_obs / ring_next / gphys are rows.obs / rows.next / rows.phys
+    RowSource rows;
     const float *ring_obs, *ring_next;
+    const int32_t* gphys;
     dqnx_ctrl* ctrl;
     bool dbl;             // streams 0 online(obs), 1 online(next) [double], 2 target(next)
     int nstreams, act, L, NC, A;
@@ -1625,8 +1710,10 @@ static StepCtx step_ctx(dqnx_engine* e, int key) {
     cx.phys = at<int32_t>(e, e->ws_phys) + (size_t)cx.slot * e->Bl;
     cx.params = at<float>(e, e->off[DQNX_BUF_PARAMS]);
     cx.tparams = at<float>(e, e->off[DQNX_BUF_TARGET_PARAMS]);
-    cx.ring_obs = at<float>(e, e->off[DQNX_BUF_RING_OBS]);
-    cx.ring_next = at<float>(e, e->off[DQNX_BUF_RING_NEXT_OBS]);
+    cx.rows = row_source(e, cx.phys);
+    cx.ring_obs = cx.rows.obs;
+    cx.ring_next = cx.rows.next;
+    cx.gphys = cx.rows.phys;
     cx.ctrl = ctrl_of(e);
     cx.dbl = e->cfg.algo != DQNX_ALGO_DQN;
     cx.nstreams = cx.dbl ? 3 : 2;
@@ -1682,7 +1769,7 @@ static void fused_steps(const StepCtx& cx, std::vector<KStep>& ks) {
     SampleArgs nxt;
     const bool sample_next = (cx.key & KEY_SAMPLE_NEXT) != 0;
     if (sample_next) nxt = staging_sample_args(cx.e);
-    build_fused_steps(cx.e, cx.flags, cx.idx, cx.phys, ks, sample_next ? &nxt : nullptr);
+    build_fused_steps(cx.e, cx.flags, cx.idx, cx.phys, cx.rows, ks, sample_next ? &nxt : nullptr);
 }
 
 // 1. sample (R:dqn/replay_memory.py:38-39; PER :69-92)
@@ -1719,6 +1806,55 @@ static void sample_steps(const StepCtx& cx, std::vector<KStep>& ks) {
     }
 }
 
+// 1b. n-step engines: materialise the step's minibatch from the ring (nstep.hip).  It reads the step's
+//     real slot table cx.phys, once that is final: behind the sampler launch, or (KEY_SAMPLE_NEXT, the
+//     side-stream pipelines) behind the copy / event that hands the step a minibatch drawn ahead.
+static void nstep_gather_step(const StepCtx& cx, std::vector<KStep>& ks) {
+    dqnx_engine* e = cx.e;
+    const dqnx_config& c = e->cfg;
+    NstepArgs na;
+    memset(&na, 0, sizeof(na));
+    na.Bl = e->Bl;
+    na.n_step = c.n_step;
+    na.n_env = c.n_env;
+    na.stride = e->stride;
+    na.stride16 = e->stride16;
+    na.tiles = (e->Bl + 15) / 16;
+    na.parts = nstep_parts(e->stride);
+    // the fused plan's forward gathers row tile t on XCD t % 8: write it there
+    if (e->bwd_plan == 2 && fused_xcd_rows(e) && e->nstep_xcd) {
+        na.xcd_rows = 1;
+        na.xcd_mr = e->fplan.mr;
+        na.xcd_shift = (fused_xcd_shift(e, (cx.key & KEY_SAMPLE_NEXT) != 0) ? 1 : 0) + (e->nstep_xcd == 2 ? 4 : 0);
+    }
+    na.gamma = c.gamma;
+    na.capacity = c.capacity;
+    na.ctrl = cx.ctrl;
+    na.phys = cx.phys;
+    na.ring_obs = at<float>(e, e->off[DQNX_BUF_RING_OBS]);
+    na.ring_next = at<float>(e, e->off[DQNX_BUF_RING_NEXT_OBS]);
+    na.ring16_obs = e->stride16 ? at<uint16_t>(e, e->ws_ring16[0]) : nullptr;
+    na.ring16_next = e->stride16 ? at<uint16_t>(e, e->ws_ring16[1]) : nullptr;
+    na.ring_act = at<int32_t>(e, e->off[DQNX_BUF_RING_ACT]);
+    na.ring_rew = at<float>(e, e->off[DQNX_BUF_RING_REW]);
+    na.ring_done = at<float>(e, e->off[DQNX_BUF_RING_DONE]);
+    na.mb_obs = at<float>(e, e->nb_obs);
+    na.mb_next = at<float>(e, e->nb_next);
+    na.mb16_obs = e->stride16 ? at<uint16_t>(e, e->nb_obs16) : nullptr;
+    na.mb16_next = e->stride16 ? at<uint16_t>(e, e->nb_next16) : nullptr;
+    na.mb_act = at<int32_t>(e, e->nb_act);
+    na.mb_rew = at<float>(e, e->nb_rew);
+    na.mb_done = at<float>(e, e->nb_done);
+    na.mb_disc = at<float>(e, e->nb_disc);
+    na.mb_phys = at<int32_t>(e, e->nb_phys);
+    na.mb_start = at<float4>(e, e->nb_start);
+    // bytes moved: both rows in and out (fp32 + the bf16 copies), per row the slot, the window's
+    // (rew, done) pairs and the action in, the five scalars and the start-row record out
+    const double row = 4.0 * e->stride + 2.0 * e->stride16;
+    const double bytes = cx.Bl * (4.0 * row + 4.0 + 8.0 * c.n_step + 4.0 + 5.0 * 4.0 + 16.0);
+    push(ks, "nstep_gather", 0, bytes, [=](hipStream_t s) { return launch_nstep_gather(na, s); });
+}
+
 // 2a'. implicit-GEMM convs, the last one writing F (conv_ig.hip)
 static void conv_ig_fwd(const StepCtx& cx, std::vector<KStep>& ks) {
     dqnx_engine* e = cx.e;
@@ -1744,7 +1880,7 @@ static void conv_ig_fwd(const StepCtx& cx, std::vector<KStep>& ks) {
         ca.act = act;
         CigSource& S = ca.src;
         if (l == 0) {   // the micro grid straight from the ring rows (CHW after the macro features)
-            S.phys = cx.phys;
+            S.phys = cx.gphys;
             S.bstride = e->stride;
             S.off = np.macro_len;
             S.pstride = 1;
@@ -1771,7 +1907,7 @@ static void conv_ig_fwd(const StepCtx& cx, std::vector<KStep>& ks) {
             ca.orow = cp.Wo;
             ca.opix = 1;
             ca.och = cp.Ho * cp.Wo;
-            ca.phys = cx.phys;
+            ca.phys = cx.gphys;
             ca.ring_stride = e->stride;
             ca.macro_len = np.macro_len;
             ca.flat_cols = cp.Co * cp.Ho * cp.Wo;
@@ -1853,7 +1989,7 @@ static void conv_micro_fwd(const StepCtx& cx, std::vector<KStep>& ks) {
     ma.ring_next = cx.ring_next;
     ma.ring_stride = e->stride;
     ma.macro_len = np.macro_len;
-    ma.phys = cx.phys;
+    ma.phys = cx.gphys;
     ma.strideF = np.strideF;
     const ConvPlan& cl = np.conv[cx.NC - 1];
     ma.flat_cols = cl.Co * cl.Ho * cl.Wo;
@@ -1911,7 +2047,7 @@ static void conv_explicit_fwd(const StepCtx& cx, std::vector<KStep>& ks) {
             p.lda = cp.Kstride;
         });
         ia.nstreams = nps;
-        ia.phys = cx.phys;
+        ia.phys = cx.gphys;
         ia.ring_stride = e->stride;
         ia.ring_off = np.macro_len;
         ia.Ci = cp.Ci; ia.Hi = cp.Hi; ia.Wi = cp.Wi; ia.Ho = cp.Ho; ia.Wo = cp.Wo;
@@ -1945,7 +2081,7 @@ static void conv_explicit_fwd(const StepCtx& cx, std::vector<KStep>& ks) {
         fl.ring[z] = st == 0 ? cx.ring_obs : cx.ring_next;
         fl.F[z] = at<float>(e, e->ws_F) + (int64_t)st * e->Bl * np.strideF;
     });
-    fl.phys = cx.phys;
+    fl.phys = cx.gphys;
     fl.ring_stride = e->stride;
     fl.macro_len = np.macro_len;
     fl.C = cl.Co; fl.Ho = cl.Ho; fl.Wo = cl.Wo;
@@ -1979,9 +2115,9 @@ static void dense_fwd_steps(const StepCtx& cx, std::vector<KStep>& ks) {
                 p.A = at<float>(e, e->ws_F) + (int64_t)st * e->Bl * np.strideF;
                 p.lda = np.strideF;
             } else if (l == 0) {
-                p.A = at<float>(e, e->off[st == 0 ? DQNX_BUF_RING_OBS : DQNX_BUF_RING_NEXT_OBS]);
+                p.A = st == 0 ? cx.ring_obs : cx.ring_next;
                 p.lda = e->stride;
-                p.phys = cx.phys;
+                p.phys = cx.gphys;
                 p.xcopy = (st == 0) ? at<float>(e, e->ws_xobs) : nullptr;
             } else {
                 const int w = np.dense[l - 1].out;
@@ -2048,13 +2184,14 @@ static void head_step(const StepCtx& cx, std::vector<KStep>& ks) {
     ha.head_params = (int)np.head_params;
     ha.inv_bg = (float)(1.0 / (double)e->Bg);
     ha.gamma = (float)c.gamma;
+    ha.disc = cx.rows.disc;
     ha.H = at<float>(e, e->ws_H[cx.L - 1]);
     ha.Wo = cx.params + np.head_off;
     ha.Wt = cx.tparams + np.head_off;
-    ha.phys = cx.phys;
-    ha.act = at<int32_t>(e, e->off[DQNX_BUF_RING_ACT]);
-    ha.rew = at<float>(e, e->off[DQNX_BUF_RING_REW]);
-    ha.done = at<float>(e, e->off[DQNX_BUF_RING_DONE]);
+    ha.phys = cx.gphys;
+    ha.act = cx.rows.act;
+    ha.rew = cx.rows.rew;
+    ha.done = cx.rows.done;
     ha.isw = (c.algo == DQNX_ALGO_PER_DOUBLE) ? at<float>(e, e->off[DQNX_BUF_IS_WEIGHTS]) + e->shard_begin : nullptr;
     ha.abs_td_out = (c.algo == DQNX_ALGO_PER_DOUBLE) ? at<float>(e, e->off[DQNX_BUF_PER_ABS_TD]) + e->shard_begin
                                                      : nullptr;
@@ -2187,7 +2324,7 @@ static void conv_ig_bwd(const StepCtx& cx, std::vector<KStep>& ks) {
         X.H = cp.Hi; X.W = cp.Wi; X.C = cp.Ci;
         if (l == 0) {
             X.base[0] = cx.ring_obs;
-            X.phys = cx.phys;
+            X.phys = cx.gphys;
             X.bstride = e->stride;
             X.off = np.macro_len;
             X.pstride = 1;
@@ -2264,7 +2401,7 @@ static void conv_micro_bwd(const StepCtx& cx, std::vector<KStep>& ks) {
     da.ring_obs = cx.ring_obs;
     da.stamps = at<int64_t>(e, e->ws_stamps);
     da.err = &ctrl_of(e)->error;
-    da.phys = cx.phys;
+    da.phys = cx.gphys;
     da.ring_stride = e->stride;
     da.macro_len = np.macro_len;
     double wf = 0, wb = 0;
@@ -2505,6 +2642,7 @@ static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
     const StepCtx cx = step_ctx(e, key);
     std::vector<KStep> ks;
     sample_steps(cx, ks);
+    if (e->nstep) nstep_gather_step(cx, ks);   // the slot table is final: every launch below reads cx.rows
     if (e->bwd_plan == 2) {
         fused_steps(cx, ks);
         return ks;
@@ -2917,6 +3055,9 @@ static int check_config(const dqnx_engine* e) {
     if (c.batch <= 0 || c.world_size <= 0 || c.rank < 0 || c.rank >= c.world_size || c.batch % c.world_size)
         return set_error(DQNX_EINVAL, "batch must be a positive multiple of world_size");
     if (c.capacity <= 0 || c.capacity >= ((int64_t)1 << 31)) return set_error(DQNX_EINVAL, "capacity out of range");
+    if (c.n_step < 1 || c.n_step > DQNX_NSTEP_MAX)
+        return set_error(DQNX_EINVAL, "n_step %d not in [1, %d]", c.n_step, DQNX_NSTEP_MAX);
+    if (c.n_step > 1 && c.n_env < 1) return set_error(DQNX_EINVAL, "n_step %d needs n_env >= 1 (got %d)", c.n_step, c.n_env);
     if (e->np.NH > 16) return set_error(DQNX_EUNSUPPORTED, "head with more than 16 outputs");
     if (!head_supported(e->np.F)) return set_error(DQNX_EUNSUPPORTED, "head input width %d not in {64,128,256}", e->np.F);
     for (size_t l = 0; l < e->np.dense.size(); l++)
@@ -3077,6 +3218,9 @@ int plan_engine(dqnx_engine* e) {
     e->Bs = e->local_sampling ? e->Bl : e->Bg;
     e->stride = (int)align_up((uint64_t)c.net.obs_dim, 4);
     e->tiles = (e->Bl + 15) / 16;
+    // n-step returns: DQNX_NSTEP_FORCE=1 sends an n_step = 1 engine through the gather too (bitwise the default)
+    e->nstep = c.n_step > 1 || (route_knob("DQNX_NSTEP_FORCE", 0) == 1 && c.n_env >= 1);
+    e->nstep_xcd = route_knob("DQNX_NSTEP_XCD", 1);
     if (e->bwd_plan == 2) plan_fused_forward(e);
     e->setsize = sample_setsize(e->Bs);
     const int L = (int)e->np.dense.size();
@@ -3164,6 +3308,7 @@ void dqnx_config_defaults(dqnx_config* c) {
     c->per_beta_start = 0.4;
     c->per_beta_end = 1.0;
     c->per_beta_steps = 2e6;
+    c->n_step = 1;
 }
 
 int dqnx_engine_create(const dqnx_config* cfg, dqnx_engine** out) {
@@ -3306,6 +3451,10 @@ int dqnx_replay_push(dqnx_engine* e, const float* obs, const int32_t* act, const
     if (n < 0 || (n > 0 && (!obs || !act || !rew || !done || !next_obs)))
         return set_error(DQNX_EINVAL, "dqnx_replay_push: bad argument");
     if (e->pf_valid) return set_error(DQNX_ESTATE, "replay push while a prefetched minibatch is pending");
+    // n-step windows step through the ring n_env rows at a time: whole time steps only
+    if (e->cfg.n_step > 1 && n % e->cfg.n_env)
+        return set_error(DQNX_EINVAL, "dqnx_replay_push: %d rows into an n_step = %d engine with n_env = %d (rows are "
+                                      "time-major, env-minor: whole time steps only)", n, e->cfg.n_step, e->cfg.n_env);
     hipStream_t s = (hipStream_t)stream;
     const int D = e->cfg.net.obs_dim;
     if (!src_on_device && n > 0 && n <= kPinnedPushRows && (int64_t)n <= e->cfg.capacity) {
@@ -5374,6 +5523,51 @@ int dqnx_grad_clip_info_get(dqnx_engine* e, dqnx_grad_clip_info* out_host, int32
     DQNX_HIP_CHECK(hipMemcpyAsync(out_host, blk, sizeof(dqnx_grad_clip_info), hipMemcpyDeviceToHost, s));
     DQNX_HIP_CHECK(hipStreamSynchronize(s));
     if (reset) DQNX_HIP_CHECK(hipMemsetAsync(blk, 0, sizeof(dqnx_grad_clip_info), s));
+    return DQNX_OK;
+}
+
+int dqnx_nstep_buffer(const dqnx_engine* e, uint64_t* offset, uint64_t* bytes) {
+    if (!e || !offset || !bytes) return set_error(DQNX_EINVAL, "null argument");
+    *offset = e->nstep ? e->nb_obs : e->off[DQNX_BUF_WORKSPACE] + e->bytes[DQNX_BUF_WORKSPACE];
+    *bytes = e->nb_bytes;
+    return DQNX_OK;
+}
+
+// Test hook: the n-step window of start position p (nstep.hpp), over arrays indexed by logical position.
+// The fold is the inline function k_nstep_gather calls, instantiated at the same NMAX the launch picks.
+int dqnx_nstep_window(const float* rew, const float* done, int64_t size, int64_t p, int32_t n_step, int32_t n_env,
+                      double gamma, float* R, float* d, float* disc, int64_t* last, int32_t* m) {
+    if (!rew || !done) return set_error(DQNX_EINVAL, "null argument");
+    if (n_step < 1 || n_step > DQNX_NSTEP_MAX || n_env < 1 || size < 1 || p < 0 || p >= size)
+        return set_error(DQNX_EINVAL, "nstep window: need 0 <= p < size, 1 <= n_step <= %d, n_env >= 1", DQNX_NSTEP_MAX);
+    const int nv = nstep_positions(size, p, n_step, n_env);
+    float rw[DQNX_NSTEP_MAX], dn[DQNX_NSTEP_MAX];
+    for (int j = 0; j < DQNX_NSTEP_MAX; j++) {
+        const int jc = j < nv ? j : nv - 1;
+        rw[j] = rew[p + (int64_t)jc * n_env];
+        dn[j] = done[p + (int64_t)jc * n_env];
+    }
+    float R_ = 0.f, d_ = 0.f, disc_ = 0.f;
+    int m_ = 0;
+    auto fold = [&](auto tag) {
+        constexpr int N = decltype(tag)::value;
+        float a[N], b[N];
+        for (int j = 0; j < N; j++) {
+            a[j] = rw[j];
+            b[j] = dn[j];
+        }
+        nstep_fold<N>(a, b, nv, gamma, &R_, &d_, &disc_, &m_);
+    };
+    if (n_step <= 1) fold(std::integral_constant<int, 1>());
+    else if (n_step <= 2) fold(std::integral_constant<int, 2>());
+    else if (n_step <= 4) fold(std::integral_constant<int, 4>());
+    else if (n_step <= 8) fold(std::integral_constant<int, 8>());
+    else fold(std::integral_constant<int, 16>());
+    if (R) *R = R_;
+    if (d) *d = d_;
+    if (disc) *disc = disc_;
+    if (last) *last = p + (int64_t)(m_ - 1) * n_env;
+    if (m) *m = m_;
     return DQNX_OK;
 }
 

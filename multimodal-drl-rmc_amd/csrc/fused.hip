@@ -721,7 +721,9 @@ constexpr int HB_SDH = 272;  // LDS row stride of bf16 dZ tiles (bf16 elements, 
 
 // BF: the chain's dZ tiles are rounded to bf16 in LDS and multiplied by bf16 blocked weights
 // (fp32 accumulate); dZ_L = dHead W_head (K = 16) and every global dZ stay fp32.
-template <int ACT, int NL, bool BF>
+// DISC (n-step engines): the TD target's discount is the row's own mb_disc[b] = fp32(gamma^m) instead of
+// a.gamma.  A template parameter, not a null test: the default engine's kernel is the code it was.
+template <int ACT, int NL, bool BF, bool DISC>
 __global__ __launch_bounds__(FT) void k_head_bwd(HeadBwdArgs a) {
     __shared__ __attribute__((aligned(16))) float dzs[2][16 * HB_SD];
     __shared__ float dh[16][17];
@@ -778,7 +780,7 @@ __global__ __launch_bounds__(FT) void k_head_bwd(HeadBwdArgs a) {
     //     then the first chain level's weight stream.  Branch-free clamped loads throughout.
     const int hb = tid >> 4, hj = tid & 15;
     const int hbc = hb < nb ? hb : nb - 1;
-    float r0 = 0.f, r1 = 0.f, r2 = 0.f, wis = 1.f;
+    float r0 = 0.f, r1 = 0.f, r2 = 0.f, wis = 1.f, gm = 0.f;
     float4 tr = make_float4(0.f, 0.f, 0.f, 0.f);
     if (tid < 256) {
         const int64_t base = (int64_t)(b0 + hbc) * 16 + hj;
@@ -787,6 +789,7 @@ __global__ __launch_bounds__(FT) void k_head_bwd(HeadBwdArgs a) {
         r2 = a.raw[(int64_t)2 * a.Bl * 16 + base];
         tr = a.trans[b0 + hbc];
         if (a.isw) wis = a.isw[b0 + hbc];
+        if constexpr (DISC) gm = a.disc[b0 + hbc];   // fp32(gamma^m) of the row's window
     }
     const WaveCols cF = wave_cols(F);
     float whv[2][4], hmask[2][4];
@@ -841,7 +844,7 @@ __global__ __launch_bounds__(FT) void k_head_bwd(HeadBwdArgs a) {
         if (act < 0 || act >= A) act = 0;
         const float rew = tr.y, done = tr.z;
         const float t1 = 1.f - done;
-        const float t2 = t1 * a.gamma;
+        const float t2 = t1 * (DISC ? gm : a.gamma);
         const float t3 = t2 * qn;
         const float y = rew + t3;
         const float qa = __shfl(q0, act, 16);
@@ -1519,14 +1522,19 @@ int launch_head_bwd(const HeadBwdArgs& a, int act, hipStream_t s) {
     if (!pow2_le4(a.nsplit) || !pow2_le4(a.xcd_mr))   // (the kernel divides by them with shifts)
         return set_error(DQNX_EINVAL, "fused head: nsplit %d / row-tile height %d must be 1, 2 or 4", a.nsplit, a.xcd_mr);
     const size_t pad = DQNX_HEAD_LDS_PAD;   // dynamic LDS on top of the static tiles (occupancy knob)
+#define HEAD_BWD_LAUNCH(ACTV, NLV, BFV, DV)                                                          \
+    do {                                                                                             \
+        if (pad > 64 * 1024) allow_lds(k_head_bwd<ACTV, NLV, BFV, DV>, 120 * 1024);                  \
+        DQNX_LAUNCH((k_head_bwd<ACTV, NLV, BFV, DV>), grid, block, pad, s, a);                       \
+    } while (0)
 #define HEAD_BWD_CASE(ACTV, NLV)                                                                     \
     do {                                                                                             \
         if (a.bf16) {                                                                                \
-            if (pad > 64 * 1024) allow_lds(k_head_bwd<ACTV, NLV, true>, 120 * 1024);                 \
-            DQNX_LAUNCH((k_head_bwd<ACTV, NLV, true>), grid, block, pad, s, a);               \
+            if (a.disc) HEAD_BWD_LAUNCH(ACTV, NLV, true, true);                                      \
+            else HEAD_BWD_LAUNCH(ACTV, NLV, true, false);                                            \
         } else {                                                                                     \
-            if (pad > 64 * 1024) allow_lds(k_head_bwd<ACTV, NLV, false>, 120 * 1024);                \
-            DQNX_LAUNCH((k_head_bwd<ACTV, NLV, false>), grid, block, pad, s, a);              \
+            if (a.disc) HEAD_BWD_LAUNCH(ACTV, NLV, false, true);                                     \
+            else HEAD_BWD_LAUNCH(ACTV, NLV, false, false);                                           \
         }                                                                                            \
     } while (0)
     const bool relu = act == DQNX_ACT_RELU;
@@ -1537,6 +1545,7 @@ int launch_head_bwd(const HeadBwdArgs& a, int act, hipStream_t s) {
         default: return set_error(DQNX_EUNSUPPORTED, "fused head: %d dense layers", a.L);
     }
 #undef HEAD_BWD_CASE
+#undef HEAD_BWD_LAUNCH
     DQNX_HIP_CHECK(hipGetLastError());
     return DQNX_OK;
 }

@@ -402,7 +402,9 @@ __global__ __launch_bounds__(256) void k_bwd_level(BwdArgs a) {
 //   (5) MFMA: dH = dHead . W_head -> dZ_L = dH (.) act'(H_L);  dW_head partial = dHead^T H_L;
 //       bias and loss partials in fixed order.
 // =====================================================================================
-template <int ACT, int F>
+// DISC (n-step engines): the TD target's discount is the row's own mb_disc[b] = fp32(gamma^m) instead of
+// a.gamma (a template parameter: the default engine's kernel is the code it was).
+template <int ACT, int F, bool DISC>
 __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
     constexpr int TS = 16, QS = 17;
     constexpr int SF = F + 8, F4 = F / 4;
@@ -411,7 +413,7 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
     __shared__ float raw[3][TS][QS];
     __shared__ float qv[3][TS][QS];
     __shared__ float dh[TS][20];
-    __shared__ float gsh[TS], lossv[TS], rsh[TS], dsh[TS], wsh[TS];
+    __shared__ float gsh[TS], lossv[TS], rsh[TS], dsh[TS], wsh[TS], gmsh[TS];
     __shared__ int ash[TS];
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -456,12 +458,13 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
         if (tid < TS) {
             const int b = tid;
             int act = 0;
-            float rew = 0.f, done = 0.f, w = 1.f;
+            float rew = 0.f, done = 0.f, w = 1.f, gm = a.gamma;
             if (b < nb) {
                 const int slot = a.phys[b0 + b];
                 act = a.act[slot];
                 rew = a.rew[slot];
                 done = a.done[slot];
+                if constexpr (DISC) gm = a.disc[b0 + b];   // fp32(gamma^m) of the row's window
                 if (a.isw) w = a.isw[b0 + b];
                 if (act < 0 || act >= A) act = 0;
             }
@@ -469,6 +472,7 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
             rsh[b] = rew;
             dsh[b] = done;
             wsh[b] = w;
+            if constexpr (DISC) gmsh[b] = gm;
         }
     }
     __syncthreads();
@@ -534,7 +538,7 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
             }
             // targets = rews + (1 - dones) * gamma * q'   (R:dqn/agent.py:216)
             const float t1 = 1.f - dsh[b];
-            const float t2 = t1 * a.gamma;
+            const float t2 = t1 * (DISC ? gmsh[b] : a.gamma);
             const float t3 = t2 * qn;
             const float y = rsh[b] + t3;
             const float qa = qv[0][b][ash[b]];
@@ -1597,8 +1601,13 @@ int launch_bwd_level(const BwdArgs& a, int act, hipStream_t s) {
 
 template <int F>
 static void launch_head_f(const HeadArgs& a, int act, int tiles, hipStream_t s) {
-    if (act == DQNX_ACT_RELU) DQNX_LAUNCH((k_head<DQNX_ACT_RELU, F>), dim3(tiles), dim3(256), 0, s, a);
-    else DQNX_LAUNCH((k_head<DQNX_ACT_ELU, F>), dim3(tiles), dim3(256), 0, s, a);
+    if (a.disc) {
+        if (act == DQNX_ACT_RELU) DQNX_LAUNCH((k_head<DQNX_ACT_RELU, F, true>), dim3(tiles), dim3(256), 0, s, a);
+        else DQNX_LAUNCH((k_head<DQNX_ACT_ELU, F, true>), dim3(tiles), dim3(256), 0, s, a);
+        return;
+    }
+    if (act == DQNX_ACT_RELU) DQNX_LAUNCH((k_head<DQNX_ACT_RELU, F, false>), dim3(tiles), dim3(256), 0, s, a);
+    else DQNX_LAUNCH((k_head<DQNX_ACT_ELU, F, false>), dim3(tiles), dim3(256), 0, s, a);
 }
 
 bool head_supported(int F) { return F == 64 || F == 128 || F == 256; }

@@ -174,6 +174,9 @@ struct HeadArgs {
     float beta1, beta2, lr;
     AdamBias ab;
     int64_t* stamps;       // diagnostic builds (-DDQNX_STAMPS)
+    // [Bl] per-row discount fp32(gamma^m) of an n-step engine (k_head<.., DISC = true>), or null: `gamma` for
+    // every row.  Last, so that every other argument keeps its offset.
+    const float* disc;
 };
 
 constexpr int kMaxSeg = 10;
@@ -591,6 +594,9 @@ struct HeadBwdArgs {
     int64_t* stamps;             // diagnostic builds (-DDQNX_STAMPS): slots 40..55
     int pp_on;                   // single-GPU PER: k_per_prep's work for this kernel's samples
     PerUpdateArgs pp;
+    // [Bl] per-row discount fp32(gamma^m) of an n-step engine (k_head_bwd<.., DISC = true>), or null: `gamma`
+    // for every row.  Last, so that every other argument keeps its offset.
+    const float* disc;
 };
 bool fused_fwd_plan(FusedFwdArgs& a, int obs_dim, bool bf16, int mr);   // fills sx/sh/buf/kpad; false if unsupported
 int fused_wblk_bytes(bool bf16, int rows, int kpad);          // one blocked weight copy
@@ -930,6 +936,36 @@ struct ClipArgs {
 void clip_geometry(int64_t n_params, int64_t* chunk, int* n_part);
 int launch_grad_sumsq(const ClipArgs& a, hipStream_t s);
 int launch_clip_coef(const ClipArgs& a, hipStream_t s);
+
+// N-step returns (nstep.hip; include/dqnx.h "n-step returns"): the launch that materialises the step's
+// minibatch from the ring.  One workgroup per (16-row tile, column part); 16 lanes per row, each moving
+// up to kNstepPieces 16-byte pieces of the row per matrix.
+constexpr int kNstepThreads = 256;
+constexpr int kNstepPieces = 8;
+constexpr int kNstepChunk = 16 * kNstepPieces;   // 16-byte pieces of a row one workgroup moves
+struct NstepArgs {
+    int Bl, n_step, n_env;
+    int stride;                  // floats of an fp32 row (ring and minibatch alike), a multiple of 4
+    int stride16;                // bf16 elements of a bf16 row, a multiple of 8; 0: the engine keeps no bf16 copies
+    int tiles, parts;            // grid: ceil(Bl / 16) x nstep_parts(stride)
+    int xcd_rows, xcd_shift, xcd_mr;   // fused plan: tile t on the forward's XCD of row tile t / xcd_mr (HeadBwdArgs)
+    double gamma;
+    int64_t capacity;
+    dqnx_ctrl* ctrl;             // ring size / write pointer; the sticky error word
+    const int32_t* phys;         // [Bl] ring slots of the sampled start rows
+    const float *ring_obs, *ring_next;
+    const uint16_t *ring16_obs, *ring16_next;
+    const int32_t* ring_act;
+    const float *ring_rew, *ring_done;
+    float *mb_obs, *mb_next;     // [Bl][stride]
+    uint16_t *mb16_obs, *mb16_next;   // [Bl][stride16]
+    int32_t* mb_act;             // [Bl] each
+    float *mb_rew, *mb_done, *mb_disc;
+    int32_t* mb_phys;            // identity
+    float4* mb_start;            // {act, rew, done, 0} of the start rows
+};
+int nstep_parts(int stride);
+int launch_nstep_gather(const NstepArgs& a, hipStream_t s);
 
 int launch_sample_uniform(const SampleArgs& a, hipStream_t s);
 int launch_idx_to_phys(const int32_t* idx, int32_t* phys, int shard_begin, int n, dqnx_ctrl* ctrl, int64_t capacity,

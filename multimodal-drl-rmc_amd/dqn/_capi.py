@@ -26,6 +26,7 @@ DQNX_MAX_DENSE, DQNX_MAX_CONV = 6, 4
 (BUF_PARAMS, BUF_TARGET_PARAMS, BUF_GRADS, BUF_ADAM_M, BUF_ADAM_V, BUF_CTRL, BUF_RING_OBS,
  BUF_RING_NEXT_OBS, BUF_RING_ACT, BUF_RING_REW, BUF_RING_DONE, BUF_SUMTREE, BUF_BATCH_IDX, BUF_Q,
  BUF_TD, BUF_IS_WEIGHTS, BUF_WORKSPACE, BUF_PER_ABS_TD, BUF_LEARN_STATS, BUF_GRAD_CLIP, BUF_COUNT) = range(21)
+NSTEP_MAX = 16         # largest Config.n_step (DQNX_NSTEP_MAX)
 DQNX_RNG_PY, DQNX_RNG_NP = 0, 1
 STEP_SOFT_UPDATE = 0x1
 STEP_GIVEN_INDICES = 0x2
@@ -39,6 +40,7 @@ DEVERR_SAMPLE_TOO_LARGE = 1
 DEVERR_EMPTY_TREE = 2
 DEVERR_PER_HANDOFF = 3
 DEVERR_FWD_PAIR_HANDOFF = 4
+DEVERR_NSTEP_STATE = 19
 DEVERR_BOUNDS = {16: "k_adam4 wide path: a float4 outside the launch's element range",
                  17: "k_adam4 wide path: a permuted conv-weight copy outside the launch's range",
                  18: "k_micro_dw: a split-K slab tile outside its conv's slabs"}
@@ -65,6 +67,7 @@ class ParamInfo(ctypes.Structure):
 class Config(ctypes.Structure):
     _fields_ = [
         ("net", NetDesc), ("algo", I32), ("batch", I32), ("world_size", I32), ("rank", I32),
+        ("n_step", I32),   # (in the four bytes that were padding in front of capacity)
         ("capacity", I64), ("gamma", ctypes.c_double), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
         ("beta2", ctypes.c_double), ("adam_eps", ctypes.c_double), ("tau", ctypes.c_double), ("n_env", I32),
         ("local_sampling", I32), ("per_eps", ctypes.c_double), ("per_alpha", ctypes.c_double),
@@ -153,6 +156,7 @@ EXPORTS = [
     "dqnx_state_bytes", "dqnx_state_save", "dqnx_state_load", "dqnx_state_inspect",
     "dqnx_learn_stats_get", "dqnx_learn_stats_reset",
     "dqnx_set_grad_clip", "dqnx_get_grad_clip", "dqnx_grad_clip_info_get",
+    "dqnx_nstep_window", "dqnx_nstep_buffer",
 ]
 
 GIL_HELD = ("dqnx_agent_learn_mt", "dqnx_agent_choose")   # entry points called with the GIL held (see lib())
@@ -243,6 +247,9 @@ def lib():
         "dqnx_set_grad_clip": ([vp, ctypes.c_double], ctypes.c_int),
         "dqnx_get_grad_clip": ([vp, P(ctypes.c_double)], ctypes.c_int),
         "dqnx_grad_clip_info_get": ([vp, P(GradClipInfo), I32, vp], ctypes.c_int),
+        "dqnx_nstep_buffer": ([vp, P(ctypes.c_uint64), P(ctypes.c_uint64)], ctypes.c_int),
+        "dqnx_nstep_window": ([vp, vp, I64, I64, I32, I32, ctypes.c_double, P(ctypes.c_float), P(ctypes.c_float),
+                               P(ctypes.c_float), P(I64), P(I32)], ctypes.c_int),
     }
     # dqnx_agent_learn_mt reads and writes random._inst's MT words in place: call it through a PyDLL
     # handle, which keeps the GIL for the call (a CDLL call releases it, and another thread's `random`

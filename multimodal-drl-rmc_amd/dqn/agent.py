@@ -84,6 +84,14 @@ def _grad_clip_env():
     return float(v) if v.strip() else None
 
 
+def _n_step_env() -> int:
+    """DQNX_N_STEP=<n>: n-step returns (1 .. 16) for every learn step, assembled from the replay ring on the
+    device at sample time (LearnEngine(n_step=...)), so an unmodified train.py gets them.  Unset or empty
+    (default): 1, the reference's one-step target."""
+    v = os.environ.get("DQNX_N_STEP", "")
+    return int(v) if v.strip() else 1
+
+
 def _summary_writer(log_dir):
     try:
         from torch.utils.tensorboard import SummaryWriter
@@ -243,7 +251,7 @@ class Agent:
                                   lr=self.lr, tau=self.target_soft_update_tau, n_env=self.n_env, device=self.device,
                                   eps_dec=self.epsilon_decay,
                                   compute_dtype=os.environ.get("DQNX_COMPUTE_DTYPE", "fp32"),
-                                  per_numpy121=_per_numpy121(), grad_clip=_grad_clip_env())
+                                  per_numpy121=_per_numpy121(), grad_clip=_grad_clip_env(), n_step=_n_step_env())
         self.online_network.bind_flat(self.engine.param_views(self.engine.params), self.engine.params, spec,
                                       engine=self.engine)
         self.target_network.bind_flat(self.engine.param_views(self.engine.target_params), self.engine.target_params,

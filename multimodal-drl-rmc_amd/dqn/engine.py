@@ -212,8 +212,12 @@ class LearnEngine:
 
     def __init__(self, spec: NetSpec, algo: str, batch: int, capacity: int, gamma=0.99, lr=1e-4,
                  tau=1e-3, n_env=1, world_size=1, rank=0, device=None, graphs=False, eps_dec=2e6,
-                 local_sampling=False, compute_dtype="fp32", per_numpy121=False, grad_clip=None):
-        """grad_clip: max_norm of torch.nn.utils.clip_grad_norm_ applied to every step's gradient before
+                 local_sampling=False, compute_dtype="fp32", per_numpy121=False, grad_clip=None, n_step=1):
+        """n_step: multi-step returns (1 .. C.NSTEP_MAX, fixed for the engine's life): a sampled row's reward,
+        done flag, discount and next state span up to n_step time steps of its environment, assembled from
+        the replay ring on the device at sample time (include/dqnx.h "n-step returns").  Rows must be pushed
+        one whole time step (n_env rows) at a time.
+        grad_clip: max_norm of torch.nn.utils.clip_grad_norm_ applied to every step's gradient before
         Adam, on the device (None or <= 0: off; set_grad_clip changes it later).
         graphs: replay each learn step as a captured HIP graph (off by default: eager launches
         measured 3-4 us faster per step, include/dqnx.h dqnx_engine_set_graphs).
@@ -237,6 +241,8 @@ class LearnEngine:
             raise ValueError(f"compute_dtype must be 'fp32' or 'bf16', got {compute_dtype!r}")
         cfg.compute_dtype = C.DQNX_COMPUTE_BF16 if compute_dtype == "bf16" else C.DQNX_COMPUTE_FP32
         cfg.per_numpy121 = 1 if per_numpy121 else 0
+        cfg.n_step = int(n_step)
+        self.n_step = int(n_step)
         self.compute_dtype = compute_dtype
         self.cfg = cfg
         h = ctypes.c_void_p()
@@ -306,6 +312,30 @@ class LearnEngine:
         o, b = self.buffer(which)
         t = self.arena[o:o + b]
         return t.view(dtype) if b else t.view(dtype)
+
+    def nstep_views(self):
+        """The minibatch the last learn step of an n-step engine materialised (the last part of the workspace,
+        in the order include/dqnx.h fixes): name -> view.  None for a default engine (it has none)."""
+        o, b = ctypes.c_uint64(), ctypes.c_uint64()
+        C.check(self.L.dqnx_nstep_buffer(self.h, ctypes.byref(o), ctypes.byref(b)), "nstep_buffer")
+        o, b = int(o.value), int(b.value)
+        if not b:
+            return None
+        Bl, S = self.batch_local, self.obs_stride
+        S16 = (self.spec.obs_dim + 7) // 8 * 8 if self.compute_dtype == "bf16" else 0
+        fields = [("mb_obs", torch.float32, (Bl, S)), ("mb_next", torch.float32, (Bl, S)), ("mb_act", torch.int32, (Bl,)),
+                  ("mb_rew", torch.float32, (Bl,)), ("mb_done", torch.float32, (Bl,)), ("mb_disc", torch.float32, (Bl,)),
+                  ("mb_phys", torch.int32, (Bl,)), ("mb_start", torch.float32, (Bl, 4))]
+        if S16:
+            fields += [("mb_obs16", torch.bfloat16, (Bl, S16)), ("mb_next16", torch.bfloat16, (Bl, S16))]
+        out, cur = {}, o
+        for name, dt, shape in fields:
+            cur = (cur + 255) // 256 * 256
+            n = int(np.prod(shape)) * torch.empty(0, dtype=dt).element_size()
+            out[name] = self.arena[cur:cur + n].view(dt).view(*shape)
+            cur += n
+        assert cur <= o + b, (cur, o, b)
+        return out
 
     def stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -768,6 +798,8 @@ def raise_device_error(err: int):
         raise RuntimeError("libdqnx: PER tree update hand-off timed out inside a launch (internal error)")
     if err == C.DEVERR_FWD_PAIR_HANDOFF:
         raise RuntimeError("libdqnx: paired-column forward hand-off timed out inside a launch (internal error)")
+    if err == C.DEVERR_NSTEP_STATE:
+        raise RuntimeError("libdqnx: the n-step gather met a ring size, write pointer or sampled slot outside the ring")
     if err in C.DEVERR_BOUNDS:
         raise RuntimeError(f"libdqnx: out-of-range write skipped (internal error): {C.DEVERR_BOUNDS[err]}")
     if err:
