@@ -580,7 +580,7 @@ typedef struct dqnx_learn_stats {
     double gap_sum;            /* top-1 minus top-2 of the DQNX_BUF_Q[0] row, subtracted in fp32 (0 when A = 1) */
     double reward_sum;         /* replay reward of the sampled rows */
     double isw_sum;            /* PER importance weights (0 for uniform replay) */
-    double loss_sum;           /* sum of dqnx_ctrl.loss */
+    double loss_sum;           /* sum of dqnx_ctrl.loss (with dqnx_set_cql on: the total, TD + regulariser) */
     double grad_norm_sum;      /* sum over steps of sqrt(sum_t grad_sq of the step) */
     double grad_norm_max;      /* its maximum (a derived fp64 value, so kept in fp64) */
     int64_t huber_linear_rows; /* rows with |delta| >= 1 (SmoothL1's linear regime, beta = 1) */
@@ -709,6 +709,48 @@ int dqnx_nstep_buffer(const dqnx_engine* e, uint64_t* offset, uint64_t* bytes);
 int dqnx_nstep_window(const float* rew, const float* done, int64_t size, int64_t p, int32_t n_step,
                       int32_t n_env, double gamma, float* R, float* d, float* disc,
                       int64_t* last, int32_t* m);
+
+/* ---- conservative Q-learning: the CQL(H) regulariser for training from a fixed dataset ----
+ * Plain (double) DQN on transitions that no longer grow over-estimates the actions the data never took.
+ * CQL(H) for discrete actions adds one term to the loss,
+ *
+ *   L = L_TD + alpha * mean_b [ logsumexp_a Q_online(s_b, a) - Q_online(s_b, a_b) ]
+ *
+ * computed in the head kernels of every learn route, from the fp32 row Q_online(s_b, .) they already hold
+ * (after the dueling aggregate).  Per sampled row, a = the clamped replay action, A = n_actions:
+ *
+ *   m    = max_j q_j
+ *   e_j  = expf(q_j - m)            libm-grade expf / logf, no contraction
+ *   s    = sum_j e_j                (the routes may sum in different orders)
+ *   gap  = (m + logf(s)) - q_a
+ *   p_j  = e_j / s
+ *   dq_j = gq [j = a] + cb (p_j - [j = a]),   cb = fp32(alpha) * (1 / B_global)
+ *
+ * gq is the TD gradient as without this section (Huber, IS-weighted under PER).  Through the head:
+ * linear d_j = dq_j; dueling d_V = sum_j dq_j, d_Aj = dq_j - (sum_j dq_j) / A.  The row's loss contribution
+ * is lb + fp32(alpha) * gap, so dqnx_ctrl.loss -- and with it dqnx_learn_stats.loss_sum -- reports the TOTAL
+ * loss.  Under PER the regulariser is NOT importance-weighted, and |delta|, the priorities and the SumTree
+ * updates are exactly the TD error's.  The 1 / B_global factor makes data-parallel shards sum to the
+ * global-batch mean like the TD term.  DQNX_BUF_TD, DQNX_BUF_Q and abs_td keep their meaning.
+ *
+ * It costs no launch, no device storage and no arena byte: with alpha > 0 a step launches exactly the
+ * launches it launches with alpha = 0 (dqnx_learn_kernel_count / _info give the same names, FLOPs and
+ * bytes); the head kernel of the step is another instantiation of the same template.  With alpha = 0 (the
+ * default) the head kernels are the code of an engine that never heard of this section, bit for bit.  It
+ * applies to every learn entry point and flag combination: dqnx_learn_step, dqnx_learn_steps,
+ * dqnx_agent_launch / dqnx_agent_learn_mt, dqnx_learn_step_bucket, dqnx_learn_step_timed / _omit; graphs,
+ * prefetch, n-step returns, gradient clipping, bf16.
+ *
+ * dqnx_set_cql: host only; alpha <= 0 means off.  NaN or an infinity: DQNX_EINVAL, the value kept.
+ *   Configuration like lr: never in the state blob, accepted by an unbound engine.  It drops the engine's
+ *   cached plans and graphs (alpha is a launch argument and picks the instantiation).  DQNX_ESTATE under
+ *   dqnx_state_save's pending conditions.
+ * dqnx_cql_row (test hook, host only, no engine, no GPU): gap and p_j - [j = a] of one row q[0 .. n_actions)
+ *   by the inline function the head kernel calls.  1 <= n_actions <= 16 (else DQNX_EINVAL); an action outside
+ *   [0, n_actions) is taken as 0, as the kernels clamp it.  q and p_minus_onehot must not overlap. */
+int dqnx_set_cql(dqnx_engine* e, double alpha);
+int dqnx_get_cql(const dqnx_engine* e, double* alpha);
+int dqnx_cql_row(const float* q, int32_t n_actions, int32_t action, float* gap, float* p_minus_onehot);
 
 /* ---- kernel-level timing (bench.py roofline) ---------------------------------------
  * A learn step is an ordered list of kernel launches (sample, linear_fwd_l1.., head_td_loss,

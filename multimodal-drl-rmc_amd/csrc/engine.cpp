@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "cql.hpp"
 #include "learn.hpp"
 #include "nstep.hpp"
 
@@ -450,6 +451,7 @@ struct dqnx_engine {
     int stats_bwg = 0, stats_rows = 0, stats_chunk = 0, stats_chunks = 0;   // stats_chunks == 0: unsupported net
     // gradient clipping (clip.hip): max_norm (<= 0: off) and the sum-of-squares launch geometry
     double grad_clip = 0.0;
+    double cql_alpha = 0.0;   // dqnx_set_cql: 0 = off; configuration like lr, never in the state blob
     int64_t clip_chunk = 0;
     int clip_parts = 0;
     // n-step returns (nstep.hip): the engine's steps read a minibatch materialised by "nstep_gather"
@@ -1254,6 +1256,7 @@ void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, c
         ha.inv_bg = (float)(1.0 / (double)e->Bg);
         ha.gamma = (float)c.gamma;
         ha.disc = rs.disc;
+        ha.cql_alpha = (float)e->cql_alpha;
         ha.params = params;
         ha.raw = at<float>(e, e->ws_raw);
         ha.trans = at<float4>(e, e->ws_trans);
@@ -2185,6 +2188,7 @@ static void head_step(const StepCtx& cx, std::vector<KStep>& ks) {
     ha.inv_bg = (float)(1.0 / (double)e->Bg);
     ha.gamma = (float)c.gamma;
     ha.disc = cx.rows.disc;
+    ha.cql_alpha = (float)e->cql_alpha;
     ha.H = at<float>(e, e->ws_H[cx.L - 1]);
     ha.Wo = cx.params + np.head_off;
     ha.Wt = cx.tparams + np.head_off;
@@ -5523,6 +5527,34 @@ int dqnx_grad_clip_info_get(dqnx_engine* e, dqnx_grad_clip_info* out_host, int32
     DQNX_HIP_CHECK(hipMemcpyAsync(out_host, blk, sizeof(dqnx_grad_clip_info), hipMemcpyDeviceToHost, s));
     DQNX_HIP_CHECK(hipStreamSynchronize(s));
     if (reset) DQNX_HIP_CHECK(hipMemsetAsync(blk, 0, sizeof(dqnx_grad_clip_info), s));
+    return DQNX_OK;
+}
+
+int dqnx_set_cql(dqnx_engine* e, double alpha) {
+    if (!e) return set_error(DQNX_EINVAL, "engine is null");
+    if (alpha != alpha || std::isinf(alpha)) return set_error(DQNX_EINVAL, "cql: alpha is not a finite number");
+    int rc = state_pending(e, "set cql");
+    if (rc) return rc;
+    const double v = alpha > 0.0 ? alpha : 0.0;
+    if (v == e->cql_alpha) return DQNX_OK;
+    e->cql_alpha = v;
+    drop_graphs(e);   // alpha is a launch argument of the cached plans and picks the head kernels' instantiation
+    return DQNX_OK;
+}
+
+int dqnx_get_cql(const dqnx_engine* e, double* alpha) {
+    if (!e || !alpha) return set_error(DQNX_EINVAL, "null argument");
+    *alpha = e->cql_alpha;
+    return DQNX_OK;
+}
+
+// Test hook: one row of the regulariser through cql.hpp's cql_row, the function k_head's thread (b, 0) calls.
+int dqnx_cql_row(const float* q, int32_t n_actions, int32_t action, float* gap, float* p_minus_onehot) {
+    if (!q || !gap || !p_minus_onehot) return set_error(DQNX_EINVAL, "null argument");
+    if (n_actions < 1 || n_actions > 16) return set_error(DQNX_EINVAL, "cql row: need 1 <= n_actions <= 16");
+    int act = action;
+    if (act < 0 || act >= n_actions) act = 0;   // as the head kernels clamp it
+    cql_row(q, n_actions, act, gap, p_minus_onehot);
     return DQNX_OK;
 }
 

@@ -25,6 +25,7 @@
 // one coalesced 1 KiB buffer_load_dwordx4 per wave per 16x16x16 block.  The 16-row
 // activation tile is shared by all waves and lives in LDS (row stride = 8 mod 64 floats:
 // conflict-free ds_read_b128 fragments, MI355X_MICROARCH.md §LDS).
+#include "cql.hpp"
 #include "learn.hpp"
 #include "per_common.hpp"
 #include "sample_body.hpp"
@@ -723,7 +724,10 @@ constexpr int HB_SDH = 272;  // LDS row stride of bf16 dZ tiles (bf16 elements, 
 // (fp32 accumulate); dZ_L = dHead W_head (K = 16) and every global dZ stay fp32.
 // DISC (n-step engines): the TD target's discount is the row's own mb_disc[b] = fp32(gamma^m) instead of
 // a.gamma.  A template parameter, not a null test: the default engine's kernel is the code it was.
-template <int ACT, int NL, bool BF, bool DISC>
+// CQL (dqnx_set_cql, alpha > 0): the conservative regulariser a.cql_alpha * (logsumexp_j Q(s, j) - Q(s, a)) joins
+// the row's loss and gradient (cql.hpp): three more 16-lane butterflies (max, sum of exp, sum of dq), one expf
+// and one logf per lane.  A template parameter for the same reason.
+template <int ACT, int NL, bool BF, bool DISC, bool CQL>
 __global__ __launch_bounds__(FT) void k_head_bwd(HeadBwdArgs a) {
     __shared__ __attribute__((aligned(16))) float dzs[2][16 * HB_SD];
     __shared__ float dh[16][17];
@@ -860,11 +864,36 @@ __global__ __launch_bounds__(FT) void k_head_bwd(HeadBwdArgs a) {
             gq = x <= -1.f ? -a.inv_bg : (x >= 1.f ? a.inv_bg : (a.inv_bg * x) / 1.f);
             lb = l;
         }
-        const float gmean = (-gq) / (float)A;
         float d = 0.f;
-        if (hj < NH) {
-            if (duel) d = (hj == 0) ? gq : ((hj - 1 == act ? gq : 0.f) + gmean);
-            else d = (hj == act) ? gq : 0.f;
+        if constexpr (CQL) {
+            // lane j: dq_j = gq [j == a] + cb (p_j - [j == a]); lanes j >= A add -inf to the max, 0 to the sums
+            float mx = hj < A ? q0 : -INFINITY;
+#pragma unroll
+            for (int m = 8; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 16));
+            const float ev = hj < A ? cql_exp(q0, mx) : 0.f;
+            float sm = ev;
+#pragma unroll
+            for (int m = 8; m >= 1; m >>= 1) sm += __shfl_xor(sm, m, 16);
+            const float gap = cql_gap(mx, sm, qa);
+            const float cb = a.cql_alpha * a.inv_bg;
+            const bool hit = hj == act;
+            const float dq = hj < A ? cql_dq(gq, cb, cql_pm(ev, sm, hit), hit) : 0.f;
+            float sdq = dq;
+#pragma unroll
+            for (int m = 8; m >= 1; m >>= 1) sdq += __shfl_xor(sdq, m, 16);
+            lb = cql_loss(lb, a.cql_alpha, gap);
+            // through the aggregate: d_V = sum_j dq_j, d_Aj = dq_j - (sum_j dq_j) / A (slot j + 1 holds A_j)
+            const float dqm = __shfl(dq, hj >= 1 ? hj - 1 : 0, 16);
+            if (hj < NH) {
+                if (duel) d = (hj == 0) ? sdq : dqm - sdq / (float)A;
+                else d = dq;
+            }
+        } else {
+            const float gmean = (-gq) / (float)A;
+            if (hj < NH) {
+                if (duel) d = (hj == 0) ? gq : ((hj - 1 == act ? gq : 0.f) + gmean);
+                else d = (hj == act) ? gq : 0.f;
+            }
         }
         const bool real = hb < nb;
         if (!real) { d = 0.f; lb = 0.f; }
@@ -1522,10 +1551,16 @@ int launch_head_bwd(const HeadBwdArgs& a, int act, hipStream_t s) {
     if (!pow2_le4(a.nsplit) || !pow2_le4(a.xcd_mr))   // (the kernel divides by them with shifts)
         return set_error(DQNX_EINVAL, "fused head: nsplit %d / row-tile height %d must be 1, 2 or 4", a.nsplit, a.xcd_mr);
     const size_t pad = DQNX_HEAD_LDS_PAD;   // dynamic LDS on top of the static tiles (occupancy knob)
+#define HEAD_BWD_LAUNCH2(ACTV, NLV, BFV, DV, CV)                                                     \
+    do {                                                                                             \
+        if (pad > 64 * 1024) allow_lds(k_head_bwd<ACTV, NLV, BFV, DV, CV>, 120 * 1024);              \
+        DQNX_LAUNCH((k_head_bwd<ACTV, NLV, BFV, DV, CV>), grid, block, pad, s, a);                   \
+    } while (0)
+    const bool cql = a.cql_alpha > 0.f;   // the one place this kernel's CQL instantiation is picked
 #define HEAD_BWD_LAUNCH(ACTV, NLV, BFV, DV)                                                          \
     do {                                                                                             \
-        if (pad > 64 * 1024) allow_lds(k_head_bwd<ACTV, NLV, BFV, DV>, 120 * 1024);                  \
-        DQNX_LAUNCH((k_head_bwd<ACTV, NLV, BFV, DV>), grid, block, pad, s, a);                       \
+        if (cql) HEAD_BWD_LAUNCH2(ACTV, NLV, BFV, DV, true);                                         \
+        else HEAD_BWD_LAUNCH2(ACTV, NLV, BFV, DV, false);                                            \
     } while (0)
 #define HEAD_BWD_CASE(ACTV, NLV)                                                                     \
     do {                                                                                             \
@@ -1546,6 +1581,7 @@ int launch_head_bwd(const HeadBwdArgs& a, int act, hipStream_t s) {
     }
 #undef HEAD_BWD_CASE
 #undef HEAD_BWD_LAUNCH
+#undef HEAD_BWD_LAUNCH2
     DQNX_HIP_CHECK(hipGetLastError());
     return DQNX_OK;
 }

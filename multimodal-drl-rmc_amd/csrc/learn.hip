@@ -14,6 +14,7 @@
 //   soft target update     R:dqn/agent.py:105-110
 #include "gemm_lds.hpp"
 #include "gemm_sk.hpp"
+#include "cql.hpp"
 #include "learn.hpp"
 #include "per_common.hpp"
 #include "mt.hpp"
@@ -404,7 +405,9 @@ __global__ __launch_bounds__(256) void k_bwd_level(BwdArgs a) {
 // =====================================================================================
 // DISC (n-step engines): the TD target's discount is the row's own mb_disc[b] = fp32(gamma^m) instead of
 // a.gamma (a template parameter: the default engine's kernel is the code it was).
-template <int ACT, int F, bool DISC>
+// CQL (dqnx_set_cql, alpha > 0): thread (b, 0) also folds the row's conservative regulariser through cql_row
+// (cql.hpp) into the LDS row cqs[b] = p_j - [j == a]; step (4) forms dq_j from it.  A template parameter too.
+template <int ACT, int F, bool DISC, bool CQL>
 __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
     constexpr int TS = 16, QS = 17;
     constexpr int SF = F + 8, F4 = F / 4;
@@ -415,6 +418,7 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
     __shared__ float dh[TS][20];
     __shared__ float gsh[TS], lossv[TS], rsh[TS], dsh[TS], wsh[TS], gmsh[TS];
     __shared__ int ash[TS];
+    float(*cqs)[QS] = raw[0];   // CQL: p_j - [j == a] of row b, over raw[0] (dead once step (2) formed Q)
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int i = lane & 15, g = lane >> 4;
@@ -553,6 +557,11 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
                 gq = x <= -1.f ? -a.inv_bg : (x >= 1.f ? a.inv_bg : (a.inv_bg * x) / 1.f);
                 lb = l;
             }
+            if constexpr (CQL) {   // never importance-weighted; |delta| and the priorities stay the TD error's
+                float gap;
+                cql_row(qv[0][b], A, ash[b], &gap, cqs[b]);
+                lb = cql_loss(lb, a.cql_alpha, gap);
+            }
             const int gb = b0 + b;
             a.td[gb] = y;
             a.td[Bl + gb] = qa;
@@ -570,7 +579,18 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
         const float gq = gsh[b];
         const int act = ash[b];
         float d = 0.f;
-        if (o < NH) {
+        if constexpr (CQL) {
+            if (o < NH && b < nb) {   // (rows >= nb never ran cql_row: their dh stays 0)
+                const float cb = a.cql_alpha * a.inv_bg;
+                if (a.head_kind == DQNX_HEAD_DUELING) {   // d_V = sum_j dq_j, d_Aj = dq_j - (sum_j dq_j) / A
+                    float sdq = 0.f;
+                    for (int j = 0; j < A; j++) sdq += cql_dq(gq, cb, cqs[b][j], j == act);
+                    d = (o == 0) ? sdq : cql_dq(gq, cb, cqs[b][o - 1], o - 1 == act) - sdq / (float)A;
+                } else {
+                    d = cql_dq(gq, cb, cqs[b][o], o == act);
+                }
+            }
+        } else if (o < NH) {
             if (a.head_kind == DQNX_HEAD_DUELING)
                 d = (o == 0) ? gq : ((o - 1 == act ? gq : 0.f) + (-gq) / (float)A);   // V / A - mean(A) bwd
             else
@@ -1601,13 +1621,20 @@ int launch_bwd_level(const BwdArgs& a, int act, hipStream_t s) {
 
 template <int F>
 static void launch_head_f(const HeadArgs& a, int act, int tiles, hipStream_t s) {
+    const bool cql = a.cql_alpha > 0.f;   // the one place this kernel's CQL instantiation is picked
+#define HEAD_LAUNCH(ACTV, DV)                                                                       \
+    do {                                                                                            \
+        if (cql) DQNX_LAUNCH((k_head<ACTV, F, DV, true>), dim3(tiles), dim3(256), 0, s, a);          \
+        else DQNX_LAUNCH((k_head<ACTV, F, DV, false>), dim3(tiles), dim3(256), 0, s, a);             \
+    } while (0)
     if (a.disc) {
-        if (act == DQNX_ACT_RELU) DQNX_LAUNCH((k_head<DQNX_ACT_RELU, F, true>), dim3(tiles), dim3(256), 0, s, a);
-        else DQNX_LAUNCH((k_head<DQNX_ACT_ELU, F, true>), dim3(tiles), dim3(256), 0, s, a);
+        if (act == DQNX_ACT_RELU) HEAD_LAUNCH(DQNX_ACT_RELU, true);
+        else HEAD_LAUNCH(DQNX_ACT_ELU, true);
         return;
     }
-    if (act == DQNX_ACT_RELU) DQNX_LAUNCH((k_head<DQNX_ACT_RELU, F, false>), dim3(tiles), dim3(256), 0, s, a);
-    else DQNX_LAUNCH((k_head<DQNX_ACT_ELU, F, false>), dim3(tiles), dim3(256), 0, s, a);
+    if (act == DQNX_ACT_RELU) HEAD_LAUNCH(DQNX_ACT_RELU, false);
+    else HEAD_LAUNCH(DQNX_ACT_ELU, false);
+#undef HEAD_LAUNCH
 }
 
 bool head_supported(int F) { return F == 64 || F == 128 || F == 256; }

@@ -177,6 +177,9 @@ struct HeadArgs {
     // [Bl] per-row discount fp32(gamma^m) of an n-step engine (k_head<.., DISC = true>), or null: `gamma` for
     // every row.  Last, so that every other argument keeps its offset.
     const float* disc;
+    // fp32(alpha) of the conservative regulariser (dqnx_set_cql): > 0 picks k_head<.., CQL = true>; 0: off, the
+    // kernel of an engine that never set it.  After disc, for the same reason.
+    float cql_alpha;
 };
 
 constexpr int kMaxSeg = 10;
@@ -597,6 +600,9 @@ struct HeadBwdArgs {
     // [Bl] per-row discount fp32(gamma^m) of an n-step engine (k_head_bwd<.., DISC = true>), or null: `gamma`
     // for every row.  Last, so that every other argument keeps its offset.
     const float* disc;
+    // fp32(alpha) of the conservative regulariser (dqnx_set_cql): > 0 picks k_head_bwd<.., CQL = true>; 0: off,
+    // the kernel of an engine that never set it.  After disc, for the same reason.
+    float cql_alpha;
 };
 bool fused_fwd_plan(FusedFwdArgs& a, int obs_dim, bool bf16, int mr);   // fills sx/sh/buf/kpad; false if unsupported
 int fused_wblk_bytes(bool bf16, int rows, int kpad);          // one blocked weight copy

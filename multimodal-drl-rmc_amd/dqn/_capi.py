@@ -157,6 +157,7 @@ EXPORTS = [
     "dqnx_learn_stats_get", "dqnx_learn_stats_reset",
     "dqnx_set_grad_clip", "dqnx_get_grad_clip", "dqnx_grad_clip_info_get",
     "dqnx_nstep_window", "dqnx_nstep_buffer",
+    "dqnx_set_cql", "dqnx_get_cql", "dqnx_cql_row",
 ]
 
 GIL_HELD = ("dqnx_agent_learn_mt", "dqnx_agent_choose")   # entry points called with the GIL held (see lib())
@@ -248,6 +249,9 @@ def lib():
         "dqnx_get_grad_clip": ([vp, P(ctypes.c_double)], ctypes.c_int),
         "dqnx_grad_clip_info_get": ([vp, P(GradClipInfo), I32, vp], ctypes.c_int),
         "dqnx_nstep_buffer": ([vp, P(ctypes.c_uint64), P(ctypes.c_uint64)], ctypes.c_int),
+        "dqnx_set_cql": ([vp, ctypes.c_double], ctypes.c_int),
+        "dqnx_get_cql": ([vp, P(ctypes.c_double)], ctypes.c_int),
+        "dqnx_cql_row": ([P(ctypes.c_float), I32, I32, P(ctypes.c_float), P(ctypes.c_float)], ctypes.c_int),
         "dqnx_nstep_window": ([vp, vp, I64, I64, I32, I32, ctypes.c_double, P(ctypes.c_float), P(ctypes.c_float),
                                P(ctypes.c_float), P(I64), P(I32)], ctypes.c_int),
     }

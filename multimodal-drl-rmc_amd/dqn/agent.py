@@ -84,6 +84,14 @@ def _grad_clip_env():
     return float(v) if v.strip() else None
 
 
+def _cql_alpha_env():
+    """DQNX_CQL_ALPHA=<alpha>: add the CQL(H) regulariser alpha * mean(logsumexp_a Q(s, a) - Q(s, a_b)) to every
+    learn step's loss (LearnEngine(cql_alpha=...)), so an unmodified train.py gets it.  Unset, empty or <= 0
+    (default): the reference's loss."""
+    v = os.environ.get("DQNX_CQL_ALPHA", "")
+    return float(v) if v.strip() else None
+
+
 def _n_step_env() -> int:
     """DQNX_N_STEP=<n>: n-step returns (1 .. 16) for every learn step, assembled from the replay ring on the
     device at sample time (LearnEngine(n_step=...)), so an unmodified train.py gets them.  Unset or empty
@@ -251,7 +259,8 @@ class Agent:
                                   lr=self.lr, tau=self.target_soft_update_tau, n_env=self.n_env, device=self.device,
                                   eps_dec=self.epsilon_decay,
                                   compute_dtype=os.environ.get("DQNX_COMPUTE_DTYPE", "fp32"),
-                                  per_numpy121=_per_numpy121(), grad_clip=_grad_clip_env(), n_step=_n_step_env())
+                                  per_numpy121=_per_numpy121(), grad_clip=_grad_clip_env(), n_step=_n_step_env(),
+                                  cql_alpha=_cql_alpha_env())
         self.online_network.bind_flat(self.engine.param_views(self.engine.params), self.engine.params, spec,
                                       engine=self.engine)
         self.target_network.bind_flat(self.engine.param_views(self.engine.target_params), self.engine.target_params,
@@ -581,6 +590,12 @@ class Agent:
         While it is on, log() writes GradNorm (the window's mean pre-clip norm) and GradClipFrac."""
         self.engine.set_grad_clip(max_norm)   # (launches a recorded step and consumes its readback first)
 
+    def set_cql_alpha(self, alpha) -> None:
+        """Weight of the CQL(H) regulariser of every following learn step (None or <= 0: off, the default;
+        DQNX_CQL_ALPHA=<alpha> sets it at construction).  While it is on, log() writes CQLGap, the last step's
+        mean logsumexp_a Q(s, a) - Q(s, a_b), and Loss is the total loss."""
+        self.engine.set_cql_alpha(alpha)   # (launches a recorded step and consumes its readback first)
+
     def _log_grad_clip(self, step):
         """The log window's clipping scalars (one blocking read, then the block is zeroed)."""
         ci = self.engine.grad_clip_info(reset=True)
@@ -629,6 +644,10 @@ class Agent:
             loss = self._log_learn_stats(self.step * self.n_env) if self.engine.collect_stats else None
             if self.engine.grad_clip > 0:
                 self._log_grad_clip(self.step * self.n_env)
+            if self.engine.cql_alpha > 0:
+                gap = self.engine.cql_gap()
+                if gap is not None:
+                    self.summary_writer.add_scalar('CQLGap', gap, global_step=self.step * self.n_env)
             self.summary_writer.add_scalar('Loss', self.engine.loss() if loss is None else loss,
                                            global_step=self.step * self.n_env)
             self.summary_writer.add_scalar('LearnTransitionsPerSec', self.learn_throughput(),

@@ -55,6 +55,15 @@ class NetSpec:
             d.conv_out[i], d.conv_kh[i], d.conv_kw[i], d.conv_sh[i], d.conv_sw[i] = f, kh, kw, sh, sw
         return d
 
+    @classmethod
+    def from_c(cls, d) -> "NetSpec":
+        """The NetSpec of a dqnx_net_desc (to_c's inverse), e.g. the one a state blob's header carries."""
+        return cls(kind=int(d.kind), head=int(d.head), activation=int(d.activation), obs_dim=int(d.obs_dim),
+                   n_actions=int(d.n_actions), dense=tuple(int(w) for w in d.dense[:d.n_dense]),
+                   macro_len=int(d.macro_len), micro_chw=(int(d.micro_c), int(d.micro_h), int(d.micro_w)),
+                   conv=tuple((int(d.conv_out[i]), (int(d.conv_kh[i]), int(d.conv_kw[i])),
+                               (int(d.conv_sh[i]), int(d.conv_sw[i]))) for i in range(d.n_conv)))
+
     def param_infos(self):
         L = C.lib()
         d = self.to_c()
@@ -212,8 +221,12 @@ class LearnEngine:
 
     def __init__(self, spec: NetSpec, algo: str, batch: int, capacity: int, gamma=0.99, lr=1e-4,
                  tau=1e-3, n_env=1, world_size=1, rank=0, device=None, graphs=False, eps_dec=2e6,
-                 local_sampling=False, compute_dtype="fp32", per_numpy121=False, grad_clip=None, n_step=1):
-        """n_step: multi-step returns (1 .. C.NSTEP_MAX, fixed for the engine's life): a sampled row's reward,
+                 local_sampling=False, compute_dtype="fp32", per_numpy121=False, grad_clip=None, n_step=1,
+                 cql_alpha=None):
+        """cql_alpha: weight of the CQL(H) regulariser alpha * mean(logsumexp_a Q(s, a) - Q(s, a_b)) added to every
+        step's loss in the head kernels, for training from a fixed dataset (None or <= 0: off; set_cql_alpha
+        changes it later; include/dqnx.h "conservative Q-learning").
+        n_step: multi-step returns (1 .. C.NSTEP_MAX, fixed for the engine's life): a sampled row's reward,
         done flag, discount and next state span up to n_step time steps of its environment, assembled from
         the replay ring on the device at sample time (include/dqnx.h "n-step returns").  Rows must be pushed
         one whole time step (n_env rows) at a time.
@@ -283,6 +296,8 @@ class LearnEngine:
         # agent_launch / agent_learn_mt steps also accumulate the training statistics (DQNX_STEP_STATS)
         self.collect_stats = False
         self.grad_clip = 0.0
+        self.cql_alpha = 0.0
+        self._stepped = False    # a learn step of this engine has filled q / td (cql_gap)
         self.ring_size = 0
         self.ring_wptr = 0
         self.agent_step = 0      # host mirror of dqnx_ctrl.agent_step (PER beta schedule)
@@ -293,6 +308,8 @@ class LearnEngine:
         self.settle_hook = None
         if grad_clip is not None:
             self.set_grad_clip(grad_clip)
+        if cql_alpha is not None:
+            self.set_cql_alpha(cql_alpha)
 
     def launch_recorded(self):
         if self.launch_hook is not None:
@@ -457,6 +474,7 @@ class LearnEngine:
         flags = (C.STEP_SOFT_UPDATE if soft_update else 0) | (C.STEP_STATS if self.collect_stats else 0)
         C.check(self.L.dqnx_agent_launch(self.h, flags, self.stream()), "agent_launch")
         self._ag_unread = True
+        self._stepped = True
         if self.cfg.algo == C.DQNX_ALGO_PER_DOUBLE:   # every PER learn step samples: step += n_env
             self.agent_step += self.cfg.n_env
 
@@ -474,6 +492,7 @@ class LearnEngine:
         C.check(self.L.dqnx_agent_learn_mt(self.h, mt_addr, pos_addr, flags, self.stream(), ctypes.byref(w)),
                 "agent_learn_mt")
         self._ag_unread = self._ag_unread or launch
+        self._stepped = self._stepped or launch
         return int(w.value)
 
     def agent_readback(self, wait: bool):
@@ -525,6 +544,7 @@ class LearnEngine:
             | (C.STEP_GRADS_ONLY if grads_only else 0) | (C.STEP_PREFETCH if prefetch else 0) \
             | (C.STEP_STATS if stats else 0)
         C.check(self.L.dqnx_learn_step(self.h, flags, self.stream()), "learn_step")
+        self._stepped = True
         if self.cfg.algo == C.DQNX_ALGO_PER_DOUBLE:   # every PER learn step samples: step += n_env
             self.agent_step += self.cfg.n_env
 
@@ -539,6 +559,7 @@ class LearnEngine:
         step's minibatch after the first drawn inside the previous step's last launch."""
         flags = (C.STEP_SOFT_UPDATE if soft_update else 0) | (C.STEP_STATS if stats else 0)
         C.check(self.L.dqnx_learn_steps(self.h, flags, int(count), self.stream()), "learn_steps")
+        self._stepped = self._stepped or int(count) > 0
         if self.cfg.algo == C.DQNX_ALGO_PER_DOUBLE:
             self.agent_step += self.cfg.n_env * int(count)
 
@@ -564,6 +585,7 @@ class LearnEngine:
         plan, bucket 0): the forward launch also draws the next step's minibatch (DQNX_STEP_PREFETCH)."""
         C.check(self.L.dqnx_learn_step_bucket(self.h, C.STEP_PREFETCH if prefetch else 0, int(bucket), self.stream()),
                 "learn_step_bucket")
+        self._stepped = True
         if bucket == 0 and self.cfg.algo == C.DQNX_ALGO_PER_DOUBLE:   # bucket 0 samples: step += n_env
             self.agent_step += self.cfg.n_env
 
@@ -678,6 +700,26 @@ class LearnEngine:
         out = ctypes.c_double()
         C.check(self.L.dqnx_get_grad_clip(self.h, ctypes.byref(out)), "get_grad_clip")
         self.grad_clip = float(out.value)
+
+    # ---- conservative Q-learning (dqnx_*_cql: include/dqnx.h "conservative Q-learning") --------------
+    def set_cql_alpha(self, alpha) -> None:
+        """Weight of the CQL(H) regulariser for every following step; None or <= 0 turns it off.
+        Configuration like lr: not part of the training-state blob."""
+        self.settle()   # a drop-in Agent's recorded step runs under the setting it was recorded with
+        v = 0.0 if alpha is None else float(alpha)
+        C.check(self.L.dqnx_set_cql(self.h, ctypes.c_double(v)), "set_cql")
+        out = ctypes.c_double()
+        C.check(self.L.dqnx_get_cql(self.h, ctypes.byref(out)), "get_cql")
+        self.cql_alpha = float(out.value)
+
+    def cql_gap(self):
+        """mean_b(logsumexp_a Q(s_b, a) - Q(s_b, a_b)) of the last learn step's (local) minibatch, computed
+        with torch from the q and td buffers: ONE blocking read, meant for log cadence.  It is the gap
+        whether or not the regulariser is on.  None before this engine's first learn step."""
+        self.launch_recorded()
+        if not self._stepped:
+            return None
+        return float((torch.logsumexp(self.q[0], 1) - self.td[1]).mean())
 
     def grad_clip_info(self, reset=False) -> dict:
         """What the clipped steps since the last reset saw: ONE blocking read, meant for log cadence.
