@@ -752,6 +752,95 @@ int dqnx_set_cql(dqnx_engine* e, double alpha);
 int dqnx_get_cql(const dqnx_engine* e, double* alpha);
 int dqnx_cql_row(const float* q, int32_t n_actions, int32_t action, float* gap, float* p_minus_onehot);
 
+/* ---- offline evaluation: sweep a range of the replay ring on the device, no update ----
+ * What a set of weights does on a fixed set of transitions: for the logical range [lo, hi) of the engine's own
+ * replay ring (0 = the oldest row, deque order) the route's forward runs over the rows IN ORDER, in chunks of
+ * batch rows, and per-row quantities are reduced to dataset totals on the device.  Nothing of the engine's
+ * training state changes: parameters, target parameters, Adam moments and step, RNG states, the ring, the
+ * SumTree and priorities, dqnx_ctrl (loss included), the learn statistics, the (idx, phys) slots and a
+ * minibatch drawn ahead (DQNX_STEP_PREFETCH: the staged minibatch and the compute slot it was copied to) are
+ * all left as they were; a dqnx_state_save blob is byte-equal before and after, and learn steps interleaved
+ * with evaluations are bitwise the uninterrupted steps.  Only scratch is written: the caller's scratch buffer,
+ * the activations / raw head outputs of DQNX_BUF_WORKSPACE that every step's forward rewrites, on an n-step
+ * engine the materialised minibatch (rewritten by every step's gather), and derived weight copies (the fused
+ * plan's blocked copies, the conv plans' permuted copies) which are REBUILT from the weights when stale,
+ * exactly as the next step would.  DQNX_BUF_Q and DQNX_BUF_TD are not written: they keep describing the last
+ * learn step (LearnEngine.cql_gap() too).
+ *
+ * Row inputs: per position p in [lo, hi) the transition the engine's learn step would train on had it sampled
+ * p -- the n-step window of "n-step returns" when n_step > 1 -- and the target rule of the engine's
+ * algorithm (DQN: the max; Double / PER-Double: the online argmax into the target net).
+ *   q_j   = Q_online(s, j) after the head's aggregate;  a = the clamped replay action
+ *   y     = R + ((1 - d) * disc) * q'          the head kernels' fp32 order
+ * Per-row quantities (fp32, csrc/eval.hpp):
+ *   delta = y - q_a
+ *   lb    = |delta| < 1 ? (0.5 |delta|) |delta| : |delta| - 0.5    Huber, beta = 1, UNWEIGHTED (no IS weights:
+ *           evaluation is not sampling), no regulariser
+ *   v     = max_j q_j;   g = the first j with q_j = v (torch's and the head kernels' tie rule)
+ *   gap   = (v + logf(sum_j expf(q_j - v))) - q_a                  logsumexp_j q_j - q_a, csrc/cql.hpp's forms
+ *   agap  = v - max_{j != g} q_j                                   the action gap; 0 when A = 1
+ * Totals: dqnx_eval_result below.  Every sum is carried in fp64 from the first add (delta^2: the exact fp64
+ * product) in a fixed order -- the 16 rows of a workgroup in row order, the workgroup records in workgroup
+ * order, the chunks in chunk order -- with no atomics on floating-point values, so two calls on the same
+ * state return the same bytes, whenever they are made.  n_actions <= DQNX_STATS_MAX_ACTIONS.
+ * Optional per-row output: rows_out = a device buffer [hi - lo][4] fp32 (16-byte aligned), row p - lo =
+ * (g, q_a, v, delta); NULL to skip.
+ *
+ * Launches per chunk c (rows lo + c*B .. , B = batch): "eval_idx" (positions and their ring slots
+ * (ring_wptr - ring_size + p) mod capacity into the scratch table; positions past hi are clamped to hi - 1,
+ * so the forward always runs a full batch of valid rows), on an n-step engine "nstep_gather" reading that
+ * table, the route's own forward launches (fused MLP plan fp32 / bf16, per-layer plan, micro-CNN, im2col and
+ * implicit-GEMM conv plans) with the table as their row source and without sampler workgroup, staged-minibatch
+ * copy, Adam scalars or MT-cache work, on the per-layer routes "eval_head" (the raw head outputs in the fused
+ * plan's [3][B][16] layout; the fused forward already leaves them), "eval_rows" (rows past the range's end
+ * contribute nothing) and "eval_fold" (a launch of its own: one workgroup sums the workgroup records and adds
+ * the chunk to the accumulator in the scratch).  Chunks accumulate on the device; the call copies the result
+ * to result_out (host memory) once and synchronises `stream` once, after the last chunk.  Plans are cached per
+ * engine and scratch pointer and dropped with the step plans.
+ *
+ * dqnx_eval_scratch_bytes: the scratch the caller allocates (device memory, 256-byte aligned): the chunk's
+ *   index / slot table, one fp64 record per 16-row workgroup, the accumulator.  The arena does not change.
+ * dqnx_eval_range refuses: DQNX_EINVAL for lo < 0, hi > ring size or lo >= hi (an n-step engine refuses no
+ *   further row: a window is cut by the ring's newest end, m >= 1, so every position is a valid start row);
+ *   DQNX_EUNSUPPORTED on a world_size > 1 engine; DQNX_ESTATE during a stream capture.
+ * dqnx_eval_kernel_count / _name / dqnx_eval_chunk_timed: the launches of one chunk, and one chunk (the rows
+ *   lo .. lo + B, totals discarded) run eagerly with the event pair bound to launch `kernel_index`.
+ * dqnx_eval_row (test hook, host only, no engine, no GPU): one row from the raw head outputs of the three
+ *   streams (n_actions entries for a linear head; V then n_actions advantages for a dueling head, n_actions
+ *   <= 15 there), serially through the inline functions k_eval_rows calls.  raw_online_next may be NULL for
+ *   DQNX_ALGO_DQN.  An action outside [0, n_actions) is taken as 0. */
+typedef struct dqnx_eval_result {
+    int64_t rows;                      /* hi - lo */
+    double huber_sum;                  /* lb */
+    double abs_td_sum, td_sq_sum;      /* |delta|, delta^2 */
+    double q_sa_sum;                   /* q_a */
+    double v_sum;                      /* max_j q_j */
+    double cql_gap_sum;                /* logsumexp_j q_j - q_a */
+    double action_gap_sum;             /* top-1 minus top-2 */
+    double reward_sum;                 /* the (n-step) reward R */
+    double target_sum;                 /* y */
+    double abs_td_max, v_max, v_min;
+    int64_t agree_rows;                /* g == a */
+    int64_t done_rows;                 /* d != 0 */
+    int64_t greedy_hist[DQNX_STATS_MAX_ACTIONS];
+    int64_t taken_hist[DQNX_STATS_MAX_ACTIONS];
+} dqnx_eval_result;
+typedef struct dqnx_eval_row_result {
+    int32_t greedy, action;            /* g; the clamped replay action */
+    float q_a, v, delta, huber, gap, action_gap, y;
+    float reserved0;                   /* 0 */
+} dqnx_eval_row_result;
+int dqnx_eval_scratch_bytes(const dqnx_engine* e, uint64_t* bytes);
+int dqnx_eval_range(dqnx_engine* e, int64_t lo, int64_t hi, void* scratch, uint64_t scratch_bytes,
+                    float* rows_out_or_null, dqnx_eval_result* result_out_host, void* stream);
+int dqnx_eval_row(const float* raw_online, const float* raw_online_next, const float* raw_target_next,
+                  int32_t head, int32_t n_actions, int32_t algo, int32_t action, float reward, float done,
+                  float discount, dqnx_eval_row_result* out);
+int dqnx_eval_kernel_count(dqnx_engine* e, int32_t* n);
+int dqnx_eval_kernel_name(dqnx_engine* e, int32_t index, char* name, int32_t name_len);
+int dqnx_eval_chunk_timed(dqnx_engine* e, int64_t lo, void* scratch, uint64_t scratch_bytes, int32_t kernel_index,
+                          void* ev_start, void* ev_stop, void* stream);
+
 /* ---- kernel-level timing (bench.py roofline) ---------------------------------------
  * A learn step is an ordered list of kernel launches (sample, linear_fwd_l1.., head_td_loss,
  * linear_bwd_lL..l1, adam_fused).  dqnx_learn_step_timed runs one whole step exactly like

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "cql.hpp"
+#include "eval.hpp"
 #include "learn.hpp"
 #include "nstep.hpp"
 
@@ -400,6 +401,18 @@ struct KStep {
     std::function<int(hipStream_t)> run;
 };
 
+// The launches of one evaluation chunk (dqnx_eval_range): the route's forward launches reading the scratch
+// table, and the arguments of eval.hip's launches around them; built once per (engine, scratch) pair.
+struct EvalPlan {
+    void* scratch = nullptr;
+    std::vector<KStep> fwd;
+    bool head = false;       // per-layer routes: "eval_head" makes the raw head outputs
+    EvalIdxArgs ia;
+    EvalHeadArgs ha;
+    EvalRowsArgs ra;
+    EvalFoldArgs fa;
+};
+
 }  // namespace dqnx
 
 using namespace dqnx;
@@ -468,6 +481,7 @@ struct dqnx_engine {
     std::map<int, hipGraphExec_t> graph_cache;
     hipStream_t capture_stream = nullptr;
     std::map<int, std::vector<KStep>> steps_cache;
+    std::unique_ptr<EvalPlan> eval_plan;      // dqnx_eval_range's launches (dropped with the step plans)
     std::map<int, DwAdam16Args> dw16_cache;   // the fused plan's k_dw_adam16 launch of each cached plan
     int building_key = 0;                     // (the plan key steps_for is building)
     // drop-in Agent fast path (dqnx_agent_*, small host pushes): engine-owned pinned blocks + events
@@ -1082,8 +1096,10 @@ bool fused_xcd_shift(const dqnx_engine* e, bool sample_next) {
 
 // Fused MLP plan (bwd_plan 2): forward of every layer + head in one launch, head / TD /
 // dZ chain in one launch, every dW in one split-K launch, then the Adam pass.
+// fwd_only (dqnx_eval_range): the forward launches alone, rows through `rs`, and nothing of a step's state
+// in them -- no Adam scalars, no sampler workgroup, no numpy MT cache extension.
 void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, const RowSource& rs,
-                       std::vector<KStep>& ks, const SampleArgs* sample_next) {
+                       std::vector<KStep>& ks, const SampleArgs* sample_next, bool fwd_only = false) {
     const dqnx_config& c = e->cfg;
     const NetPlan& np = e->np;
     const int L = (int)np.dense.size();
@@ -1145,8 +1161,8 @@ void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, c
         fa.stamps = at<int64_t>(e, e->ws_stamps);
         fa.xcd_rows = xcd_rows ? 1 : 0;
         fa.lds_min = 1024 * tuning_knob("DQNX_FWD_LDSKB", 0);
-        fa.adam_ctrl = ctrl;   // (the head kernel below gets no ctrl: the forward stores the scalars)
-        if (e->ws_npc && c.algo == DQNX_ALGO_PER_DOUBLE && !(e->fsplit > 1 && L >= 2 && fa.mr == 1)) {
+        fa.adam_ctrl = fwd_only ? nullptr : ctrl;   // (the head kernel below gets no ctrl: the forward stores the scalars)
+        if (!fwd_only && e->ws_npc && c.algo == DQNX_ALGO_PER_DOUBLE && !(e->fsplit > 1 && L >= 2 && fa.mr == 1)) {
             fa.npc = at<uint32_t>(e, e->ws_npc);   // the next PER sample's MT blocks, twisted ahead
             fa.np_state = ctrl->np_mt;
             fa.npc_blocks = np_cache_blocks(e->Bg);
@@ -1223,6 +1239,7 @@ void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, c
             ks.push_back(k);
         }
     }
+    if (fwd_only) return;
     // 3. head / TD / Huber / dZ chain (R:dqn/agent.py:209-221; PER :259-267)
     {
         HeadBwdArgs ha;
@@ -2671,6 +2688,90 @@ static std::vector<KStep> build_compute_steps(dqnx_engine* e, int key) {
     return ks;
 }
 
+// ---- offline evaluation (include/dqnx.h "offline evaluation") -------------------------------------------
+// The caller's scratch: [idx B | phys B | one EvalPartial per 16-row tile | the accumulator], each part at
+// the next multiple of 256 bytes.
+struct EvalScratch {
+    uint64_t idx, phys, part, acc, total;
+};
+static EvalScratch eval_scratch(const dqnx_engine* e) {
+    EvalScratch y;
+    const uint64_t tiles = (uint64_t)(e->Bl + 15) / 16;
+    y.idx = 0;
+    y.phys = align_up((uint64_t)e->Bl * 4, 256);
+    y.part = y.phys + align_up((uint64_t)e->Bl * 4, 256);
+    y.acc = y.part + align_up(tiles * sizeof(EvalPartial), 256);
+    y.total = y.acc + align_up(sizeof(dqnx_eval_result), 256);
+    return y;
+}
+
+// The forward-only plan of the engine's route: the step builders above with the chunk's scratch table as the
+// row source (an n-step engine: "nstep_gather" first, reading that table), cut before the head kernel.  No
+// sampler launch, no sampler workgroup, no staged-minibatch copy: the key carries neither KEY_SAMPLE_NEXT nor
+// a slot, and nothing here reads the engine's (idx, phys) slots.
+static std::unique_ptr<EvalPlan> build_eval_plan(dqnx_engine* e, void* scratch) {
+    std::unique_ptr<EvalPlan> pl(new EvalPlan());
+    const EvalScratch y = eval_scratch(e);
+    char* sc = (char*)scratch;
+    pl->scratch = scratch;
+    StepCtx cx = step_ctx(e, 0);
+    cx.idx = reinterpret_cast<int32_t*>(sc + y.idx);
+    cx.phys = reinterpret_cast<int32_t*>(sc + y.phys);
+    cx.rows = row_source(e, cx.phys);
+    cx.ring_obs = cx.rows.obs;
+    cx.ring_next = cx.rows.next;
+    cx.gphys = cx.rows.phys;
+    std::vector<KStep>& ks = pl->fwd;
+    if (e->nstep) nstep_gather_step(cx, ks);
+    if (e->bwd_plan == 2) {
+        build_fused_steps(e, 0, cx.idx, cx.phys, cx.rows, ks, nullptr, /*fwd_only*/ true);
+    } else {
+        if (cx.NC && e->conv_ig) conv_ig_fwd(cx, ks);
+        else if (cx.NC && e->micro) conv_micro_fwd(cx, ks);
+        else if (cx.NC) conv_explicit_fwd(cx, ks);
+        dense_fwd_steps(cx, ks);
+        pl->head = true;
+    }
+    const NetPlan& np = e->np;
+    memset(&pl->ia, 0, sizeof(pl->ia));
+    pl->ia.n = e->Bl;
+    pl->ia.capacity = e->cfg.capacity;
+    pl->ia.ctrl = cx.ctrl;
+    pl->ia.idx = cx.idx;
+    pl->ia.phys = cx.phys;
+    memset(&pl->ha, 0, sizeof(pl->ha));
+    pl->ha.Bl = e->Bl;
+    pl->ha.F = np.F;
+    pl->ha.A = cx.A;
+    pl->ha.NH = np.NH;
+    pl->ha.head_kind = e->cfg.net.head;
+    pl->ha.nstreams = for_streams(cx.dbl, [&](int z, int st) { pl->ha.stream_of[z] = st; });
+    pl->ha.H = at<float>(e, e->ws_H[cx.L - 1]);
+    pl->ha.Wo = cx.params + np.head_off;
+    pl->ha.Wt = cx.tparams + np.head_off;
+    pl->ha.raw = at<float>(e, e->ws_raw);
+    memset(&pl->ra, 0, sizeof(pl->ra));
+    pl->ra.Bl = e->Bl;
+    pl->ra.A = cx.A;
+    pl->ra.NH = np.NH;
+    pl->ra.head_kind = e->cfg.net.head;
+    pl->ra.dbl = cx.dbl ? 1 : 0;
+    pl->ra.gamma = (float)e->cfg.gamma;
+    pl->ra.raw = at<float>(e, e->ws_raw);
+    pl->ra.trans = e->bwd_plan == 2 ? at<float4>(e, e->ws_trans) : nullptr;   // (the fused forward stores them)
+    pl->ra.phys = cx.rows.phys;
+    pl->ra.act = cx.rows.act;
+    pl->ra.rew = cx.rows.rew;
+    pl->ra.done = cx.rows.done;
+    pl->ra.disc = cx.rows.disc;
+    pl->ra.part = reinterpret_cast<EvalPartial*>(sc + y.part);
+    memset(&pl->fa, 0, sizeof(pl->fa));
+    pl->fa.nparts = (e->Bl + 15) / 16;
+    pl->fa.part = pl->ra.part;
+    pl->fa.acc = reinterpret_cast<dqnx_eval_result*>(sc + y.acc);
+    return pl;
+}
+
 int enqueue_range(const std::vector<KStep>& ks, int a, int b, hipStream_t s) {
     for (int i = a; i < b; i++) {
         int rc = ks[i].run(s);
@@ -2954,6 +3055,7 @@ void drop_graphs(dqnx_engine* e) {
     e->timed_cache.clear();
     e->steps_cache.clear();
     e->dw16_cache.clear();
+    e->eval_plan.reset();
 }
 
 const std::vector<KStep>& steps_for(dqnx_engine* e, int key) {
@@ -5556,6 +5658,187 @@ int dqnx_cql_row(const float* q, int32_t n_actions, int32_t action, float* gap, 
     if (act < 0 || act >= n_actions) act = 0;   // as the head kernels clamp it
     cql_row(q, n_actions, act, gap, p_minus_onehot);
     return DQNX_OK;
+}
+
+// ---- offline evaluation ------------------------------------------------------------------------------
+// Test hook: one row through eval.hpp's eval_row, the serial form of what k_eval_rows folds with 16 lanes.
+int dqnx_eval_row(const float* raw_online, const float* raw_online_next, const float* raw_target_next, int32_t head,
+                  int32_t n_actions, int32_t algo, int32_t action, float reward, float done, float discount,
+                  dqnx_eval_row_result* out) {
+    if (!raw_online || !raw_target_next || !out) return set_error(DQNX_EINVAL, "null argument");
+    if (head != DQNX_HEAD_LINEAR && head != DQNX_HEAD_DUELING) return set_error(DQNX_EINVAL, "eval row: bad head kind");
+    const int maxa = head == DQNX_HEAD_DUELING ? 15 : 16;
+    if (n_actions < 1 || n_actions > maxa) return set_error(DQNX_EINVAL, "eval row: need 1 <= n_actions <= %d", maxa);
+    if (algo != DQNX_ALGO_DQN && algo != DQNX_ALGO_DOUBLE && algo != DQNX_ALGO_PER_DOUBLE)
+        return set_error(DQNX_EINVAL, "eval row: bad algorithm");
+    const bool dbl = algo != DQNX_ALGO_DQN;
+    if (dbl && !raw_online_next) return set_error(DQNX_EINVAL, "null argument");
+    int act = action;
+    if (act < 0 || act >= n_actions) act = 0;   // as the head kernels clamp it
+    const EvalRow r = eval_row(raw_online, raw_online_next, raw_target_next, head, n_actions, dbl, act, reward, done, discount);
+    memset(out, 0, sizeof(*out));
+    out->greedy = r.g;
+    out->action = r.act;
+    out->q_a = r.qa;
+    out->v = r.v;
+    out->delta = r.delta;
+    out->huber = r.lb;
+    out->gap = r.gap;
+    out->action_gap = r.agap;
+    out->y = r.y;
+    return DQNX_OK;
+}
+
+int dqnx_eval_scratch_bytes(const dqnx_engine* e, uint64_t* bytes) {
+    if (!e || !bytes) return set_error(DQNX_EINVAL, "null argument");
+    *bytes = eval_scratch(e).total;
+    return DQNX_OK;
+}
+
+static int eval_refused(const dqnx_engine* e, const void* scratch, uint64_t scratch_bytes) {
+    if (e->cfg.world_size > 1) return set_error(DQNX_EUNSUPPORTED, "evaluation on a data-parallel engine (world_size > 1)");
+    if (e->cfg.net.n_actions > DQNX_STATS_MAX_ACTIONS)
+        return set_error(DQNX_EUNSUPPORTED, "evaluation needs n_actions <= %d", DQNX_STATS_MAX_ACTIONS);
+    if (!scratch) return set_error(DQNX_EINVAL, "null argument");
+    if (((uintptr_t)scratch) % 256) return set_error(DQNX_EINVAL, "eval scratch must be 256-byte aligned");
+    if (scratch_bytes < eval_scratch(e).total)
+        return set_error(DQNX_EINVAL, "eval scratch too small: %llu < %llu", (unsigned long long)scratch_bytes,
+                         (unsigned long long)eval_scratch(e).total);
+    return DQNX_OK;
+}
+
+static EvalPlan& eval_plan_for(dqnx_engine* e, void* scratch) {
+    if (!e->eval_plan || e->eval_plan->scratch != scratch) e->eval_plan = build_eval_plan(e, scratch);
+    return *e->eval_plan;
+}
+
+// The launches of chunk c of [lo, hi), in order; `timed` >= 0 binds the armed event pair to that launch's
+// dispatch (dqnx_eval_chunk_timed).  names: fill with the launch names instead of launching.
+static int eval_chunk(dqnx_engine* e, EvalPlan& pl, int64_t lo, int64_t hi, int64_t c, float* rows_out, hipStream_t s,
+                      int timed, hipEvent_t ev0, hipEvent_t ev1, std::vector<std::string>* names) {
+    const int64_t B = e->Bl, n = hi - lo, chunks = (n + B - 1) / B;
+    int k = 0, rc = DQNX_OK;
+    auto step = [&](const std::string& name, const std::function<int(hipStream_t)>& run) {
+        if (rc) return;
+        if (names) {
+            names->push_back(name);
+            return;
+        }
+        KernelTimer& kt = kernel_timer();
+        if (k == timed) {
+            kt.start = ev0;
+            kt.stop = ev1;
+        }
+        rc = run(s);
+        if (k == timed) {
+            if (!rc && kt.start) rc = set_error(DQNX_EUNSUPPORTED, "launch %d (%s) launches nothing through DQNX_LAUNCH", k, name.c_str());
+            kt.start = kt.stop = nullptr;
+        }
+        k++;
+    };
+    EvalIdxArgs ia = pl.ia;
+    ia.lo = lo;
+    ia.hi = hi;
+    ia.first = lo + c * B;
+    step("eval_idx", [&](hipStream_t cs) { return launch_eval_idx(ia, cs); });
+    for (const KStep& ks : pl.fwd) {
+        // the conv weights' permuted copies: once per call is enough (no weight changes inside it)
+        if (c > 0 && timed < 0 && !names && ks.name == "conv_perm") continue;
+        step(ks.name, ks.run);
+    }
+    if (pl.head) step("eval_head", [&](hipStream_t cs) { return launch_eval_head(pl.ha, cs); });
+    EvalRowsArgs ra = pl.ra;
+    ra.valid = (int)std::min<int64_t>(B, n - c * B);
+    ra.rows_out = rows_out ? rows_out + c * B * 4 : nullptr;
+    step("eval_rows", [&](hipStream_t cs) { return launch_eval_rows(ra, cs); });
+    EvalFoldArgs fa = pl.fa;
+    fa.first = c == 0;
+    fa.last = c == chunks - 1;
+    fa.rows = n;
+    step("eval_fold", [&](hipStream_t cs) { return launch_eval_fold(fa, cs); });
+    return rc;
+}
+
+static int eval_begin(dqnx_engine* e, int64_t lo, int64_t hi, void* scratch, uint64_t scratch_bytes, hipStream_t s) {
+    int rc = check_bound(e);
+    if (rc) return rc;
+    rc = eval_refused(e, scratch, scratch_bytes);
+    if (rc) return rc;
+    // (an n-step engine: every position has m >= 1 window positions -- the window is cut by the ring's newest
+    // end -- so no row of a valid range is refused)
+    if (lo < 0 || hi > e->ring_size || lo >= hi)
+        return set_error(DQNX_EINVAL, "eval range [%lld, %lld) not inside the ring's %lld rows", (long long)lo, (long long)hi,
+                         (long long)e->ring_size);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    DQNX_HIP_CHECK(hipStreamIsCapturing(s, &cs));
+    if (cs != hipStreamCaptureStatusNone) return set_error(DQNX_ESTATE, "evaluation during a stream capture");
+    // the fused plan's blocked weight copies, if the weights changed outside a pass that keeps them: rebuilt
+    // here exactly as the next step's sampler launch would (the same bytes; that step then skips the rebuild)
+    if (relayout_due(e)) {
+        rc = enqueue_relayout(e, s);
+        if (rc) return rc;
+        e->wblk_dirty = false;
+    }
+    return DQNX_OK;
+}
+
+int dqnx_eval_range(dqnx_engine* e, int64_t lo, int64_t hi, void* scratch, uint64_t scratch_bytes, float* rows_out,
+                    dqnx_eval_result* result_out, void* stream) {
+    if (!e) return set_error(DQNX_EINVAL, "engine is null");
+    if (!result_out) return set_error(DQNX_EINVAL, "null argument");
+    if (((uintptr_t)rows_out) % 16) return set_error(DQNX_EINVAL, "eval rows output must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    int rc = eval_begin(e, lo, hi, scratch, scratch_bytes, s);
+    if (rc) return rc;
+    EvalPlan& pl = eval_plan_for(e, scratch);
+    const int64_t B = e->Bl, chunks = (hi - lo + B - 1) / B;
+    for (int64_t c = 0; c < chunks; c++) {
+        rc = eval_chunk(e, pl, lo, hi, c, rows_out, s, -1, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+    }
+    DQNX_HIP_CHECK(hipMemcpyAsync(result_out, pl.fa.acc, sizeof(dqnx_eval_result), hipMemcpyDeviceToHost, s));
+    DQNX_HIP_CHECK(hipStreamSynchronize(s));
+    return DQNX_OK;
+}
+
+int dqnx_eval_kernel_count(dqnx_engine* e, int32_t* n) {
+    int rc = check_bound(e);
+    if (rc) return rc;
+    if (!n) return set_error(DQNX_EINVAL, "null argument");
+    std::vector<std::string> names;
+    EvalPlan& pl = eval_plan_for(e, e->eval_plan ? e->eval_plan->scratch : nullptr);
+    rc = eval_chunk(e, pl, 0, e->Bl, 0, nullptr, nullptr, -1, nullptr, nullptr, &names);
+    *n = (int32_t)names.size();
+    return rc;
+}
+
+int dqnx_eval_kernel_name(dqnx_engine* e, int32_t index, char* name, int32_t name_len) {
+    int rc = check_bound(e);
+    if (rc) return rc;
+    if (!name || name_len < 1) return set_error(DQNX_EINVAL, "null argument");
+    std::vector<std::string> names;
+    EvalPlan& pl = eval_plan_for(e, e->eval_plan ? e->eval_plan->scratch : nullptr);
+    rc = eval_chunk(e, pl, 0, e->Bl, 0, nullptr, nullptr, -1, nullptr, nullptr, &names);
+    if (rc) return rc;
+    if (index < 0 || index >= (int32_t)names.size()) return set_error(DQNX_EINVAL, "kernel index %d out of range", index);
+    snprintf(name, (size_t)name_len, "%s", names[index].c_str());
+    return DQNX_OK;
+}
+
+int dqnx_eval_chunk_timed(dqnx_engine* e, int64_t lo, void* scratch, uint64_t scratch_bytes, int32_t kernel_index,
+                          void* ev_start, void* ev_stop, void* stream) {
+    if (!e) return set_error(DQNX_EINVAL, "engine is null");
+    if (!ev_start || !ev_stop || kernel_index < 0) return set_error(DQNX_EINVAL, "null event or bad kernel index");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hi = std::min<int64_t>(lo + e->Bl, e->ring_size);
+    int rc = eval_begin(e, lo, hi, scratch, scratch_bytes, s);
+    if (rc) return rc;
+    EvalPlan& pl = eval_plan_for(e, scratch);
+    std::vector<std::string> names;
+    rc = eval_chunk(e, pl, lo, hi, 0, nullptr, s, -1, nullptr, nullptr, &names);
+    if (rc) return rc;
+    if (kernel_index >= (int32_t)names.size()) return set_error(DQNX_EINVAL, "kernel index %d out of range", kernel_index);
+    return eval_chunk(e, pl, lo, hi, 0, nullptr, s, kernel_index, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, nullptr);
 }
 
 int dqnx_nstep_buffer(const dqnx_engine* e, uint64_t* offset, uint64_t* bytes) {

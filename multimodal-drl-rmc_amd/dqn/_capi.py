@@ -113,6 +113,24 @@ class GradClipInfo(ctypes.Structure):
                 ("last_norm", ctypes.c_float), ("last_coef", ctypes.c_float)]
 
 
+# offline evaluation (dqnx.h "offline evaluation")
+class EvalResult(ctypes.Structure):
+    _fields_ = [
+        ("rows", I64), ("huber_sum", ctypes.c_double), ("abs_td_sum", ctypes.c_double), ("td_sq_sum", ctypes.c_double),
+        ("q_sa_sum", ctypes.c_double), ("v_sum", ctypes.c_double), ("cql_gap_sum", ctypes.c_double),
+        ("action_gap_sum", ctypes.c_double), ("reward_sum", ctypes.c_double), ("target_sum", ctypes.c_double),
+        ("abs_td_max", ctypes.c_double), ("v_max", ctypes.c_double), ("v_min", ctypes.c_double),
+        ("agree_rows", I64), ("done_rows", I64),
+        ("greedy_hist", I64 * STATS_MAX_ACTIONS), ("taken_hist", I64 * STATS_MAX_ACTIONS),
+    ]
+
+
+class EvalRowResult(ctypes.Structure):
+    _fields_ = [("greedy", I32), ("action", I32), ("q_a", ctypes.c_float), ("v", ctypes.c_float),
+                ("delta", ctypes.c_float), ("huber", ctypes.c_float), ("gap", ctypes.c_float),
+                ("action_gap", ctypes.c_float), ("y", ctypes.c_float), ("reserved0", ctypes.c_float)]
+
+
 # training-state snapshot (dqnx.h "training-state snapshot")
 STATE_MAGIC = 0x54415453584E5144   # b"DQNXSTAT" little-endian
 STATE_VERSION = 1
@@ -158,6 +176,8 @@ EXPORTS = [
     "dqnx_set_grad_clip", "dqnx_get_grad_clip", "dqnx_grad_clip_info_get",
     "dqnx_nstep_window", "dqnx_nstep_buffer",
     "dqnx_set_cql", "dqnx_get_cql", "dqnx_cql_row",
+    "dqnx_eval_scratch_bytes", "dqnx_eval_range", "dqnx_eval_row", "dqnx_eval_kernel_count",
+    "dqnx_eval_kernel_name", "dqnx_eval_chunk_timed",
 ]
 
 GIL_HELD = ("dqnx_agent_learn_mt", "dqnx_agent_choose")   # entry points called with the GIL held (see lib())
@@ -252,6 +272,13 @@ def lib():
         "dqnx_set_cql": ([vp, ctypes.c_double], ctypes.c_int),
         "dqnx_get_cql": ([vp, P(ctypes.c_double)], ctypes.c_int),
         "dqnx_cql_row": ([P(ctypes.c_float), I32, I32, P(ctypes.c_float), P(ctypes.c_float)], ctypes.c_int),
+        "dqnx_eval_scratch_bytes": ([vp, P(ctypes.c_uint64)], ctypes.c_int),
+        "dqnx_eval_range": ([vp, I64, I64, vp, ctypes.c_uint64, vp, P(EvalResult), vp], ctypes.c_int),
+        "dqnx_eval_row": ([P(ctypes.c_float), P(ctypes.c_float), P(ctypes.c_float), I32, I32, I32, I32,
+                           ctypes.c_float, ctypes.c_float, ctypes.c_float, P(EvalRowResult)], ctypes.c_int),
+        "dqnx_eval_kernel_count": ([vp, P(I32)], ctypes.c_int),
+        "dqnx_eval_kernel_name": ([vp, I32, ctypes.c_char_p, I32], ctypes.c_int),
+        "dqnx_eval_chunk_timed": ([vp, I64, vp, ctypes.c_uint64, I32, vp, vp, vp], ctypes.c_int),
         "dqnx_nstep_window": ([vp, vp, I64, I64, I32, I32, ctypes.c_double, P(ctypes.c_float), P(ctypes.c_float),
                                P(ctypes.c_float), P(I64), P(I32)], ctypes.c_int),
     }

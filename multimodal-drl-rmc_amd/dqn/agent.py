@@ -596,6 +596,11 @@ class Agent:
         mean logsumexp_a Q(s, a) - Q(s, a_b), and Loss is the total loss."""
         self.engine.set_cql_alpha(alpha)   # (launches a recorded step and consumes its readback first)
 
+    def evaluate_replay(self, lo=0, hi=None) -> dict:
+        """What the current weights do on the replay rows [lo, hi) (0 = oldest; None: every row): the dict of
+        LearnEngine.evaluate, swept on the device with nothing of the training state touched."""
+        return self.engine.evaluate(lo, hi)   # (launches a recorded step first)
+
     def _log_grad_clip(self, step):
         """The log window's clipping scalars (one blocking read, then the block is zeroed)."""
         ci = self.engine.grad_clip_info(reset=True)

@@ -721,6 +721,50 @@ class LearnEngine:
             return None
         return float((torch.logsumexp(self.q[0], 1) - self.td[1]).mean())
 
+    # ---- offline evaluation (dqnx_eval_*: include/dqnx.h "offline evaluation") ---------------------
+    def eval_scratch(self) -> torch.Tensor:
+        """The scratch dqnx_eval_range works in, allocated once and kept on the engine."""
+        if getattr(self, "_eval_scratch", None) is None:
+            n = ctypes.c_uint64()
+            C.check(self.L.dqnx_eval_scratch_bytes(self.h, ctypes.byref(n)), "eval_scratch_bytes")
+            self._eval_scratch = torch.zeros(int(n.value) + 256, dtype=torch.uint8, device=self.device)
+        t = self._eval_scratch
+        pad = (-t.data_ptr()) % 256
+        return t[pad:pad + t.numel() - 256]
+
+    def evaluate_raw(self, lo=0, hi=None, rows_out: Optional[torch.Tensor] = None) -> C.EvalResult:
+        self.launch_recorded()
+        hi = self.ring_size if hi is None else int(hi)
+        sc = self.eval_scratch()
+        out = C.EvalResult()
+        rp = ctypes.c_void_p(rows_out.data_ptr()) if rows_out is not None else None
+        C.check(self.L.dqnx_eval_range(self.h, int(lo), hi, ctypes.c_void_p(sc.data_ptr()), sc.numel(), rp,
+                                       ctypes.byref(out), self.stream()), "eval_range")
+        return out
+
+    def evaluate(self, lo=0, hi=None, rows=False):
+        """What the engine's weights do on the replay rows [lo, hi) (logical positions, 0 = oldest; hi = None:
+        the ring's size), swept in order on the device with nothing of the training state touched: a dict of
+        counts and means -- rows, loss (mean Huber of the TD error, unweighted), abs_td_mean, td_rms, abs_td_max,
+        q_sa_mean, v_mean / v_max / v_min (max_a Q), cql_gap (mean logsumexp_a Q - Q(s, a)), action_gap_mean,
+        reward_mean, target_mean, agree_rows / agree (greedy == logged action), done_rows, greedy_hist,
+        taken_hist.  ONE blocking read.  rows=True: (dict, tensor [hi - lo, 4] of (greedy, q_a, v, delta))."""
+        hi = self.ring_size if hi is None else int(hi)
+        per_row = None
+        if rows:
+            per_row = torch.empty((max(hi - int(lo), 0), 4), dtype=torch.float32, device=self.device)
+        st = self.evaluate_raw(lo, hi, per_row)
+        n = max(int(st.rows), 1)
+        A = self.spec.n_actions
+        d = {"rows": int(st.rows), "loss": st.huber_sum / n, "abs_td_mean": st.abs_td_sum / n,
+             "td_rms": (st.td_sq_sum / n) ** 0.5, "abs_td_max": float(st.abs_td_max), "q_sa_mean": st.q_sa_sum / n,
+             "v_mean": st.v_sum / n, "v_max": float(st.v_max), "v_min": float(st.v_min),
+             "cql_gap": st.cql_gap_sum / n, "action_gap_mean": st.action_gap_sum / n,
+             "reward_mean": st.reward_sum / n, "target_mean": st.target_sum / n,
+             "agree_rows": int(st.agree_rows), "agree": int(st.agree_rows) / n, "done_rows": int(st.done_rows),
+             "greedy_hist": [int(x) for x in st.greedy_hist[:A]], "taken_hist": [int(x) for x in st.taken_hist[:A]]}
+        return (d, per_row) if rows else d
+
     def grad_clip_info(self, reset=False) -> dict:
         """What the clipped steps since the last reset saw: ONE blocking read, meant for log cadence.
         steps, clipped_steps (coef < 1), norm_sum / norm_max / last_norm (the PRE-clip global norm),

@@ -8,6 +8,13 @@ the actions the data never took; set_cql_alpha turns on the CQL(H) regulariser t
 
     eng = offline.engine_from_state("run.dqnx", batch=1024, lr=3e-4, cql_alpha=1.0)
     log = offline.fit(eng, 20000, log_every=1000)
+
+A validation signal without a simulator: evaluate() sweeps a range of a ring with the current weights on the
+device and touches nothing of the training state (include/dqnx.h "offline evaluation"); split() makes a
+training and a held-out engine from one saved ring, and fit(validate=...) reports val_* at its boundaries.
+
+    train, val = offline.split("run.dqnx", holdout=20000, batch=1024, cql_alpha=1.0)
+    log = offline.fit(train, 20000, log_every=1000, validate=val, validate_every=1000)
 """
 import ctypes
 from typing import List, Optional
@@ -54,23 +61,99 @@ def engine_from_state(path_or_blob, algo: Optional[str] = None, batch: Optional[
     return eng
 
 
-def fit(engine: LearnEngine, steps: int, soft_update: bool = True, log_every: int = 0) -> List[dict]:
+def ring_rows(engine: LearnEngine):
+    """The engine's replay rows in logical order (0 = oldest) as host arrays (obs, act, rew, done, next_obs),
+    read through the ring buffer views."""
+    engine.launch_recorded()
+    n, cap = engine.ring_size, engine.capacity
+    slots = (torch.arange(n, device=engine.device) + (engine.ring_wptr - n)) % cap
+    D = engine.spec.obs_dim
+    return (engine.ring_obs[slots, :D].cpu().numpy(), engine.ring_act[slots].cpu().numpy(),
+            engine.ring_rew[slots].cpu().numpy(), engine.ring_done[slots].cpu().numpy() != 0,
+            engine.ring_next_obs[slots, :D].cpu().numpy())
+
+
+def _refill(engine: LearnEngine, rows, lo: int, hi: int) -> None:
+    """The engine's ring := rows [lo, hi): the parameters and both RNG states stay, the ring, the Adam state
+    and (prioritised engines) the priorities start fresh, as dqnx_engine_reset leaves them."""
+    rng = [engine.get_rng(w) for w in (C.DQNX_RNG_PY, C.DQNX_RNG_NP)]
+    engine.reset()
+    for w, st in zip((C.DQNX_RNG_PY, C.DQNX_RNG_NP), rng):
+        engine.set_rng(w, st)
+    step = max(engine.cfg.n_env, 1) * max(1, 4096 // max(engine.cfg.n_env, 1))   # whole time steps per push
+    for a in range(lo, hi, step):
+        b = min(a + step, hi)
+        engine.push(*[r[a:b] for r in rows])
+
+
+def split(path_or_blob, holdout: int, **kw):
+    """(train, val): two engines from one saved ring.  The validation ring is the newest `holdout` rows,
+    rounded down to whole time steps (n_env rows, kw's n_env or 1), the training ring the rows before them,
+    both in the saved order.  Both engines are engine_from_state(path_or_blob, **kw) -- the blob's parameters
+    and RNG states -- refilled through the ring buffer views and replay_push; their Adam state (and a
+    prioritised engine's priorities) start fresh."""
+    blob = _read_blob(path_or_blob)
+    train = engine_from_state(blob, **kw)
+    val = engine_from_state(blob, **kw)
+    n_env = max(int(kw.get("n_env", 1)), 1)
+    n = train.ring_size
+    hold = int(holdout) // n_env * n_env
+    if hold < 1 or hold >= n:
+        raise ValueError(f"holdout of {holdout} rows (whole time steps: {hold}) leaves no split of {n} rows")
+    rows = ring_rows(train)
+    _refill(train, rows, 0, n - hold)
+    _refill(val, rows, n - hold, n)
+    return train, val
+
+
+def evaluate(engine: LearnEngine, data: Optional[LearnEngine] = None, lo: int = 0, hi: Optional[int] = None) -> dict:
+    """engine's weights on replay rows [lo, hi): LearnEngine.evaluate on the engine's own ring, or (data: another
+    engine of the same network whose ring holds the validation transitions) on data's ring after copying the
+    online and target parameters into it.  Nothing of `engine` changes; of `data` only its parameters."""
+    if data is None or data is engine:
+        return engine.evaluate(lo, hi)
+    engine.launch_recorded()
+    data.launch_recorded()
+    data.params.copy_(engine.params)
+    data.target_params.copy_(engine.target_params)
+    data.params_modified()
+    return data.evaluate(lo, hi)
+
+
+def fit(engine: LearnEngine, steps: int, soft_update: bool = True, log_every: int = 0,
+        validate: Optional[LearnEngine] = None, validate_every: int = 0) -> List[dict]:
     """`steps` learn steps on the engine's ring, in learn_steps calls of at most FIT_CHUNK (cut at the log
     boundaries), bitwise the same as that many learn_step(soft_update) calls.  log_every > 0: after every
     log_every-th step (and after the last) one record {"step", "loss", "cql_gap", "q_sa_mean"} of that
     step is read from the device (step counts from 1 within this call; cql_gap is the mean logsumexp_a
-    Q(s, a) - Q(s, a_b) whether or not the regulariser is on).  No other host work."""
+    Q(s, a) - Q(s, a_b) whether or not the regulariser is on).  No other host work.
+    validate_every > 0: after every validate_every-th step (and after the last) the weights are evaluated on
+    `validate`'s ring (None: the engine's own) with evaluate(); the record of that boundary -- a new one if
+    log_every made none -- gains val_loss, val_cql_gap, val_agree, val_q_sa_mean, val_v_mean and val_abs_td_mean.
+    The learn steps are bitwise what they are without validation."""
     out: List[dict] = []
     done, steps = 0, int(steps)
+    validate_every = int(validate_every)
     while done < steps:
         n = min(FIT_CHUNK, steps - done)
         if log_every > 0:
             n = min(n, log_every - done % log_every)
+        if validate_every > 0:
+            n = min(n, validate_every - done % validate_every)
         engine.learn_steps(n, soft_update=soft_update)
         done += n
-        if log_every > 0 and (done % log_every == 0 or done == steps):
+        logged = log_every > 0 and (done % log_every == 0 or done == steps)
+        if logged:
             torch.cuda.synchronize(engine.device)
             engine.check_device_error()
             out.append({"step": done, "loss": engine.loss(), "cql_gap": engine.cql_gap(),
                         "q_sa_mean": float(engine.td[1].mean())})
+        if validate_every > 0 and (done % validate_every == 0 or done == steps):
+            if not logged:
+                out.append({"step": done})
+            ev = evaluate(engine, validate)
+            engine.check_device_error()
+            out[-1].update({"val_loss": ev["loss"], "val_cql_gap": ev["cql_gap"], "val_agree": ev["agree"],
+                            "val_q_sa_mean": ev["q_sa_mean"], "val_v_mean": ev["v_mean"],
+                            "val_abs_td_mean": ev["abs_td_mean"]})
     return out
