@@ -164,6 +164,9 @@ typedef struct dqnx_ctrl {
 /* n-step engines: the gather launch met a ring size / write pointer / sampled slot outside the ring (the row
  * then reads a one-position window at a clamped slot: every access stays inside the ring) */
 #define DQNX_DEVERR_NSTEP_STATE 19
+/* fitted Q evaluation: a sampled row's entry of the target-policy table (dqnx_set_target_policy) lies outside
+ * [0, n_actions); the row was computed with action 0 */
+#define DQNX_DEVERR_TPOL_ACTION 20
 
 /* ---- engine lifetime --------------------------------------------------------------- */
 typedef struct dqnx_engine dqnx_engine;
@@ -840,6 +843,90 @@ int dqnx_eval_kernel_count(dqnx_engine* e, int32_t* n);
 int dqnx_eval_kernel_name(dqnx_engine* e, int32_t index, char* name, int32_t name_len);
 int dqnx_eval_chunk_timed(dqnx_engine* e, int64_t lo, void* scratch, uint64_t scratch_bytes, int32_t kernel_index,
                           void* ev_start, void* ev_stop, void* stream);
+
+/* ---- fitted Q evaluation: score a fixed policy on the logged transitions, on the device ----
+ * dqnx_eval_range reports properties of a Q function; fitted Q evaluation (FQE) estimates the discounted return
+ * of a POLICY pi from the logged data alone: fit a fresh Q network to
+ *   y = r + ((1 - d) * gamma) * Q_target(s', pi(s'))
+ * and report the mean of Q(s0, pi(s0)) over episode-start states.  pi and the dataset are fixed, so pi(s) and
+ * pi(s') are computed once per ring slot and the fit needs no policy network.
+ *
+ * The policy-action table: a caller-allocated device buffer int32 [capacity][2] (not part of the arena),
+ * indexed by PHYSICAL ring slot: [slot][0] = argmax_j Q_pi(obs[slot], j), [slot][1] = argmax_j
+ * Q_pi(next_obs[slot], j), the first maximum (torch's rule) of the Q row after the head's aggregate.
+ *
+ * dqnx_policy_sweep: pi = the engine's ONLINE network.  Fills the table entries of the logical range
+ *   [lo, hi) in chunks of batch rows: "eval_idx", the route's own forward launches over the chunk's scratch
+ *   table with the Double stream set (online(s), online(s'), target(s')) whatever the engine's algorithm, on
+ *   the per-layer routes "eval_head", then "policy_rows" (16 lanes per row, two first-maximum butterflies, one
+ *   8-byte store per row; rows past the range's end store nothing).  Always 1-step rows: no "nstep_gather",
+ *   even on an n-step engine.  Nothing of the training state changes, exactly as under dqnx_eval_range.
+ *   Refusals: dqnx_eval_range's, DQNX_EINVAL for table_slots != capacity or a null / misaligned (8 bytes)
+ *   table, and DQNX_EUNSUPPORTED on a DQNX_ALGO_DQN engine with conv layers: its conv workspace and split-K
+ *   plans are sized for two streams, and the arena does not grow for this call.
+ * dqnx_policy_scratch_bytes: the scratch of both sweeps (= dqnx_eval_scratch_bytes).
+ *
+ * dqnx_set_target_policy: host only, no stream.  With a table set every learn step's target is
+ *     y = r + ((1 - d) * gamma) * Q_target(s', table[phys_b][1])
+ *   and the step runs the DQN stream set (online(s), target(s'): no online(s') stream, even on a Double
+ *   engine; DQNX_BUF_Q[1] is left unwritten, as on a DQNX_ALGO_DQN engine).  Loss, PER weighting, |delta|,
+ *   priorities, SumTree updates, clipping, statistics and the soft update are what they were.  The head
+ *   kernels' instantiation changes (template parameter TPOL), so the call drops the cached plans and graphs.
+ *   An entry outside [0, n_actions) met by a sampled row -- or a sampled slot outside the table, for which
+ *   nothing is read -- sets DQNX_DEVERR_TPOL_ACTION (sticky) and that row uses action 0.  dqnx_eval_range is not
+ *   affected by a table: it keeps the engine's own target rule.  NULL restores the engine's own rule.  The table is never in the state blob; the caller
+ *   keeps it alive while it is set.  Refusals: DQNX_EINVAL for table_slots != capacity; DQNX_EUNSUPPORTED
+ *   together with dqnx_set_cql(alpha > 0) -- in either order of the two setters --, with n_step > 1 (an
+ *   uncorrected n-step return follows the behaviour policy for n - 1 steps: it would evaluate a mixture of
+ *   pi and the behaviour policy, not pi) and with world_size > 1; DQNX_ESTATE under dqnx_set_cql's pending
+ *   conditions.  While a table is set dqnx_replay_push and dqnx_state_load return DQNX_ESTATE: they would
+ *   make the table stale.
+ *
+ * dqnx_fqe_range: the number FQE exists for, over the logical range [lo, hi), same plan shape: "eval_idx",
+ *   the forward (online(s), target(s')), "eval_head" where needed, "fqe_rows", "fqe_fold".  Per row p (fp32):
+ *     q_pi     = Q_online(s_p, table[slot][0])
+ *     delta_pi = r + ((1 - d) * gamma) * Q_target(s'_p, table[slot][1]) - Q_online(s_p, a_p)
+ *     huber    = the unweighted Huber (beta = 1) of delta_pi
+ *   Row p is an EPISODE START when p < n_env or done[p - n_env] != 0: p - n_env is the previous transition
+ *   of the same environment ("n-step returns": rows are time-major, env-minor), read through the
+ *   logical-to-physical mapping.  The oldest n_env rows therefore count as starts even if the ring cut their
+ *   episode.  Table entries outside [0, n_actions) are read as 0 (no error word: nothing here is stateful).
+ *   Sums in fp64 in a fixed order (rows of a workgroup, workgroup records, chunks), no floating-point atomics:
+ *   two calls on the same state return the same bytes.  rows_out: device [hi - lo][2] fp32 (q_pi, delta_pi),
+ *   8-byte aligned, or NULL.  Refusals as dqnx_policy_sweep (any algorithm and route is accepted).
+ * dqnx_fqe_kernel_count / _name / dqnx_fqe_chunk_timed: the launches of one chunk of the policy sweep
+ *   (which = 0) or of dqnx_fqe_range (which = 1), as dqnx_eval_chunk_timed.
+ * dqnx_fqe_row (test hook, host only): one row through csrc/fqe.hpp's serial forms: pi_s / pi_next from the
+ *   policy's raw head outputs (first maximum), then the row quantities from the raw outputs of online(s) and
+ *   target(s').  Dueling: V then n_actions advantages, n_actions <= 15. */
+typedef struct dqnx_fqe_result {
+    int64_t rows;                      /* hi - lo */
+    int64_t start_rows;                /* episode starts among them */
+    double q_pi_sum;                   /* q_pi over all rows */
+    double q_pi_start_sum;             /* q_pi over start rows */
+    double abs_td_sum;                 /* |delta_pi| */
+    double huber_sum;
+    double q_pi_max, q_pi_min;
+} dqnx_fqe_result;
+typedef struct dqnx_fqe_row_result {
+    int32_t pi_s, pi_next;
+    float q_pi, delta, huber, y;
+    float reserved0, reserved1;        /* 0 */
+} dqnx_fqe_row_result;
+int dqnx_policy_scratch_bytes(const dqnx_engine* e, uint64_t* bytes);
+int dqnx_policy_sweep(dqnx_engine* e, int64_t lo, int64_t hi, void* scratch, uint64_t scratch_bytes, int32_t* table,
+                      int64_t table_slots, void* stream);
+int dqnx_set_target_policy(dqnx_engine* e, const int32_t* table_or_null, int64_t table_slots);
+int dqnx_get_target_policy(const dqnx_engine* e, const int32_t** table, int64_t* table_slots);
+int dqnx_fqe_range(dqnx_engine* e, int64_t lo, int64_t hi, void* scratch, uint64_t scratch_bytes, const int32_t* table,
+                   int64_t table_slots, float* rows_out_or_null, dqnx_fqe_result* result_out_host, void* stream);
+int dqnx_fqe_row(const float* raw_online, const float* raw_target_next, const float* raw_policy,
+                 const float* raw_policy_next, int32_t head, int32_t n_actions, int32_t action, float reward,
+                 float done, float gamma, dqnx_fqe_row_result* out);
+int dqnx_fqe_kernel_count(dqnx_engine* e, int32_t which, int32_t* n);
+int dqnx_fqe_kernel_name(dqnx_engine* e, int32_t which, int32_t index, char* name, int32_t name_len);
+int dqnx_fqe_chunk_timed(dqnx_engine* e, int32_t which, int64_t lo, void* scratch, uint64_t scratch_bytes, int32_t* table,
+                         int64_t table_slots, int32_t kernel_index, void* ev_start, void* ev_stop, void* stream);
 
 /* ---- kernel-level timing (bench.py roofline) ---------------------------------------
  * A learn step is an ordered list of kernel launches (sample, linear_fwd_l1.., head_td_loss,

@@ -20,6 +20,7 @@
 
 #include "cql.hpp"
 #include "eval.hpp"
+#include "fqe.hpp"
 #include "learn.hpp"
 #include "nstep.hpp"
 
@@ -413,6 +414,20 @@ struct EvalPlan {
     EvalFoldArgs fa;
 };
 
+// The launches of one chunk of the two fitted-Q-evaluation sweeps (dqnx_policy_sweep, dqnx_fqe_range): the
+// route's forward over the chunk's scratch table -- 1-step ring rows, the Double stream set for the policy
+// sweep, the DQN stream set for the value sweep -- and the arguments of the launches around it.
+struct FqePlan {
+    void* scratch = nullptr;
+    std::vector<KStep> fwd_pol, fwd_val;
+    bool head = false;
+    EvalIdxArgs ia;
+    EvalHeadArgs ha_pol, ha_val;
+    PolicyRowsArgs pa;
+    FqeRowsArgs ra;
+    FqeFoldArgs fa;
+};
+
 }  // namespace dqnx
 
 using namespace dqnx;
@@ -465,6 +480,9 @@ struct dqnx_engine {
     // gradient clipping (clip.hip): max_norm (<= 0: off) and the sum-of-squares launch geometry
     double grad_clip = 0.0;
     double cql_alpha = 0.0;   // dqnx_set_cql: 0 = off; configuration like lr, never in the state blob
+    // dqnx_set_target_policy: the caller's slot-indexed table (fitted Q evaluation), or null: the engine's own
+    // target rule.  Configuration like cql_alpha; with it the step runs the DQN stream set (step_dbl)
+    const int32_t* tpol = nullptr;
     int64_t clip_chunk = 0;
     int clip_parts = 0;
     // n-step returns (nstep.hip): the engine's steps read a minibatch materialised by "nstep_gather"
@@ -482,6 +500,7 @@ struct dqnx_engine {
     hipStream_t capture_stream = nullptr;
     std::map<int, std::vector<KStep>> steps_cache;
     std::unique_ptr<EvalPlan> eval_plan;      // dqnx_eval_range's launches (dropped with the step plans)
+    std::unique_ptr<FqePlan> fqe_plan;        // dqnx_policy_sweep's / dqnx_fqe_range's launches (likewise)
     std::map<int, DwAdam16Args> dw16_cache;   // the fused plan's k_dw_adam16 launch of each cached plan
     int building_key = 0;                     // (the plan key steps_for is building)
     // drop-in Agent fast path (dqnx_agent_*, small host pushes): engine-owned pinned blocks + events
@@ -1055,9 +1074,10 @@ struct RowSource {
     const float* disc;                // per-row discount of an n-step engine, or null: (float)gamma
 };
 
-RowSource row_source(dqnx_engine* e, const int32_t* phys) {
+// ring: the 1-step ring rows through `phys` even on an n-step engine (the fitted-Q-evaluation sweeps)
+RowSource row_source(dqnx_engine* e, const int32_t* phys, bool ring = false) {
     RowSource rs;
-    if (e->nstep) {
+    if (e->nstep && !ring) {
         rs.phys = at<int32_t>(e, e->nb_phys);
         rs.obs = at<float>(e, e->nb_obs);
         rs.next = at<float>(e, e->nb_next);
@@ -1094,12 +1114,17 @@ bool fused_xcd_shift(const dqnx_engine* e, bool sample_next) {
     return sample_next || (e->ws_npc && e->cfg.algo == DQNX_ALGO_PER_DOUBLE);
 }
 
+// The learn step's stream set: online(s), online(s') [Double], target(s').  With a target-policy table set
+// (dqnx_set_target_policy) the target's action is a property of the row: no online(s') stream on any engine.
+static bool step_dbl(const dqnx_engine* e) { return e->cfg.algo != DQNX_ALGO_DQN && !e->tpol; }
+
 // Fused MLP plan (bwd_plan 2): forward of every layer + head in one launch, head / TD /
 // dZ chain in one launch, every dW in one split-K launch, then the Adam pass.
 // fwd_only (dqnx_eval_range): the forward launches alone, rows through `rs`, and nothing of a step's state
-// in them -- no Adam scalars, no sampler workgroup, no numpy MT cache extension.
+// in them -- no Adam scalars, no sampler workgroup, no numpy MT cache extension.  streams (fwd_only): 3 / 2
+// forces the Double / DQN stream set (the fitted-Q-evaluation sweeps), -1 the step's own.
 void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, const RowSource& rs,
-                       std::vector<KStep>& ks, const SampleArgs* sample_next, bool fwd_only = false) {
+                       std::vector<KStep>& ks, const SampleArgs* sample_next, bool fwd_only = false, int streams = -1) {
     const dqnx_config& c = e->cfg;
     const NetPlan& np = e->np;
     const int L = (int)np.dense.size();
@@ -1109,7 +1134,7 @@ void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, c
     float* params = at<float>(e, e->off[DQNX_BUF_PARAMS]);
     float* tparams = at<float>(e, e->off[DQNX_BUF_TARGET_PARAMS]);
     const double Bl = e->Bl;
-    const bool dbl = c.algo != DQNX_ALGO_DQN;
+    const bool dbl = streams < 0 ? step_dbl(e) : streams == 3;
     const int nstreams = dbl ? 3 : 2;
     double body_flops = 0, wbytes = 0;   // per stream: 2 * in * out summed; weight bytes
     for (int l = 0; l < L; l++) {
@@ -1261,7 +1286,7 @@ void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, c
         ha.NH = np.NH;
         ha.F = np.F;
         ha.head_kind = c.net.head;
-        ha.algo = c.algo;
+        ha.algo = e->tpol ? (int)DQNX_ALGO_DQN : c.algo;   // (the kernel's stream set; PER rides on isw below)
         for (int l = 0; l < L; l++) {
             ha.in[l] = np.dense[l].in;
             ha.out[l] = np.dense[l].out;
@@ -1274,6 +1299,9 @@ void build_fused_steps(dqnx_engine* e, int flags, int32_t* idx, int32_t* phys, c
         ha.gamma = (float)c.gamma;
         ha.disc = rs.disc;
         ha.cql_alpha = (float)e->cql_alpha;
+        ha.tpol = e->tpol;
+        ha.tpol_slots = c.capacity;
+        ha.err = &ctrl->error;
         ha.params = params;
         ha.raw = at<float>(e, e->ws_raw);
         ha.trans = at<float4>(e, e->ws_trans);
@@ -1735,7 +1763,7 @@ static StepCtx step_ctx(dqnx_engine* e, int key) {
     cx.ring_next = cx.rows.next;
     cx.gphys = cx.rows.phys;
     cx.ctrl = ctrl_of(e);
-    cx.dbl = e->cfg.algo != DQNX_ALGO_DQN;
+    cx.dbl = step_dbl(e);
     cx.nstreams = cx.dbl ? 3 : 2;
     cx.act = e->cfg.net.activation;
     cx.L = (int)e->np.dense.size();
@@ -2200,12 +2228,14 @@ static void head_step(const StepCtx& cx, std::vector<KStep>& ks) {
     ha.A = cx.A;
     ha.NH = np.NH;
     ha.head_kind = c.net.head;
-    ha.algo = c.algo;
+    ha.algo = e->tpol ? (int)DQNX_ALGO_DQN : c.algo;   // (the kernel's stream set; PER rides on isw below)
     ha.head_params = (int)np.head_params;
     ha.inv_bg = (float)(1.0 / (double)e->Bg);
     ha.gamma = (float)c.gamma;
     ha.disc = cx.rows.disc;
     ha.cql_alpha = (float)e->cql_alpha;
+    ha.tpol = e->tpol;
+    ha.tpol_slots = c.capacity;
     ha.H = at<float>(e, e->ws_H[cx.L - 1]);
     ha.Wo = cx.params + np.head_off;
     ha.Wt = cx.tparams + np.head_off;
@@ -2721,10 +2751,14 @@ static std::unique_ptr<EvalPlan> build_eval_plan(dqnx_engine* e, void* scratch) 
     cx.ring_obs = cx.rows.obs;
     cx.ring_next = cx.rows.next;
     cx.gphys = cx.rows.phys;
+    // the engine's own algorithm, whether or not a target-policy table is set (step_dbl is the learn step's):
+    // evaluation reports the Double / DQN rule it documents
+    cx.dbl = e->cfg.algo != DQNX_ALGO_DQN;
+    cx.nstreams = cx.dbl ? 3 : 2;
     std::vector<KStep>& ks = pl->fwd;
     if (e->nstep) nstep_gather_step(cx, ks);
     if (e->bwd_plan == 2) {
-        build_fused_steps(e, 0, cx.idx, cx.phys, cx.rows, ks, nullptr, /*fwd_only*/ true);
+        build_fused_steps(e, 0, cx.idx, cx.phys, cx.rows, ks, nullptr, /*fwd_only*/ true, cx.nstreams);
     } else {
         if (cx.NC && e->conv_ig) conv_ig_fwd(cx, ks);
         else if (cx.NC && e->micro) conv_micro_fwd(cx, ks);
@@ -2769,6 +2803,85 @@ static std::unique_ptr<EvalPlan> build_eval_plan(dqnx_engine* e, void* scratch) 
     pl->fa.nparts = (e->Bl + 15) / 16;
     pl->fa.part = pl->ra.part;
     pl->fa.acc = reinterpret_cast<dqnx_eval_result*>(sc + y.acc);
+    return pl;
+}
+
+// ---- fitted Q evaluation (include/dqnx.h "fitted Q evaluation") ---------------------------------------
+// Both sweeps' plans over the evaluation scratch layout (FqePartial fits EvalPartial's place): the forward as
+// build_eval_plan builds it, but always over the 1-step ring rows (no "nstep_gather") and with a forced stream
+// set -- Double for the policy sweep (pol: skipped where policy_refused refuses it), DQN for the value sweep.
+static std::unique_ptr<FqePlan> build_fqe_plan(dqnx_engine* e, void* scratch, bool pol) {
+    std::unique_ptr<FqePlan> pl(new FqePlan());
+    const EvalScratch y = eval_scratch(e);
+    char* sc = (char*)scratch;
+    pl->scratch = scratch;
+    const NetPlan& np = e->np;
+    auto forward = [&](bool dbl, std::vector<KStep>& ks, EvalHeadArgs& ha) {
+        StepCtx cx = step_ctx(e, 0);
+        cx.idx = reinterpret_cast<int32_t*>(sc + y.idx);
+        cx.phys = reinterpret_cast<int32_t*>(sc + y.phys);
+        cx.rows = row_source(e, cx.phys, /*ring*/ true);
+        cx.ring_obs = cx.rows.obs;
+        cx.ring_next = cx.rows.next;
+        cx.gphys = cx.rows.phys;
+        cx.dbl = dbl;
+        cx.nstreams = dbl ? 3 : 2;
+        if (e->bwd_plan == 2) {
+            build_fused_steps(e, 0, cx.idx, cx.phys, cx.rows, ks, nullptr, /*fwd_only*/ true, cx.nstreams);
+        } else {
+            if (cx.NC && e->conv_ig) conv_ig_fwd(cx, ks);
+            else if (cx.NC && e->micro) conv_micro_fwd(cx, ks);
+            else if (cx.NC) conv_explicit_fwd(cx, ks);
+            dense_fwd_steps(cx, ks);
+            pl->head = true;
+        }
+        memset(&ha, 0, sizeof(ha));
+        ha.Bl = e->Bl;
+        ha.F = np.F;
+        ha.A = cx.A;
+        ha.NH = np.NH;
+        ha.head_kind = e->cfg.net.head;
+        ha.nstreams = for_streams(dbl, [&](int z, int st) { ha.stream_of[z] = st; });
+        ha.H = at<float>(e, e->ws_H[cx.L - 1]);
+        ha.Wo = cx.params + np.head_off;
+        ha.Wt = cx.tparams + np.head_off;
+        ha.raw = at<float>(e, e->ws_raw);
+        return cx;
+    };
+    if (pol) forward(true, pl->fwd_pol, pl->ha_pol);
+    const StepCtx cx = forward(false, pl->fwd_val, pl->ha_val);
+    memset(&pl->ia, 0, sizeof(pl->ia));
+    pl->ia.n = e->Bl;
+    pl->ia.capacity = e->cfg.capacity;
+    pl->ia.ctrl = cx.ctrl;
+    pl->ia.idx = cx.idx;
+    pl->ia.phys = cx.phys;
+    memset(&pl->pa, 0, sizeof(pl->pa));
+    pl->pa.Bl = e->Bl;
+    pl->pa.A = cx.A;
+    pl->pa.head_kind = e->cfg.net.head;
+    pl->pa.slots = e->cfg.capacity;
+    pl->pa.raw = at<float>(e, e->ws_raw);
+    pl->pa.phys = cx.phys;
+    memset(&pl->ra, 0, sizeof(pl->ra));
+    pl->ra.Bl = e->Bl;
+    pl->ra.A = cx.A;
+    pl->ra.head_kind = e->cfg.net.head;
+    pl->ra.n_env = std::max(1, (int)e->cfg.n_env);
+    pl->ra.gamma = (float)e->cfg.gamma;
+    pl->ra.capacity = e->cfg.capacity;
+    pl->ra.ctrl = cx.ctrl;
+    pl->ra.raw = at<float>(e, e->ws_raw);
+    pl->ra.trans = e->bwd_plan == 2 ? at<float4>(e, e->ws_trans) : nullptr;   // (the fused forward stores them)
+    pl->ra.phys = cx.phys;
+    pl->ra.act = cx.rows.act;
+    pl->ra.rew = cx.rows.rew;
+    pl->ra.done = cx.rows.done;
+    pl->ra.part = reinterpret_cast<FqePartial*>(sc + y.part);
+    memset(&pl->fa, 0, sizeof(pl->fa));
+    pl->fa.nparts = (e->Bl + 15) / 16;
+    pl->fa.part = pl->ra.part;
+    pl->fa.acc = reinterpret_cast<dqnx_fqe_result*>(sc + y.acc);
     return pl;
 }
 
@@ -3056,6 +3169,7 @@ void drop_graphs(dqnx_engine* e) {
     e->steps_cache.clear();
     e->dw16_cache.clear();
     e->eval_plan.reset();
+    e->fqe_plan.reset();
 }
 
 const std::vector<KStep>& steps_for(dqnx_engine* e, int key) {
@@ -3552,6 +3666,7 @@ constexpr int kPinnedPushRows = 64;   // host pushes up to this many rows take t
 
 int dqnx_replay_push(dqnx_engine* e, const float* obs, const int32_t* act, const float* rew, const uint8_t* done,
                      const float* next_obs, int32_t n, int32_t src_on_device, void* stream) {
+    if (e && e->tpol) return set_error(DQNX_ESTATE, "replay push while a target-policy table is set (its entries would go stale)");
     int rc = check_bound(e);
     if (rc) return rc;
     if (n < 0 || (n > 0 && (!obs || !act || !rew || !done || !next_obs)))
@@ -5489,6 +5604,7 @@ int dqnx_state_save(dqnx_engine* e, void* dst_host, uint64_t bytes, uint64_t* wr
                          (int)c.net.field)
 
 int dqnx_state_load(dqnx_engine* e, const void* src_host, uint64_t bytes, void* stream) {
+    if (e && e->tpol) return set_error(DQNX_ESTATE, "state load while a target-policy table is set (its entries would go stale)");
     int rc = check_bound(e);
     if (rc) return rc;
     rc = state_pending(e, "state load");
@@ -5638,6 +5754,8 @@ int dqnx_set_cql(dqnx_engine* e, double alpha) {
     int rc = state_pending(e, "set cql");
     if (rc) return rc;
     const double v = alpha > 0.0 ? alpha : 0.0;
+    if (v > 0.0 && e->tpol)   // (dqnx_set_target_policy refuses the other order)
+        return set_error(DQNX_EUNSUPPORTED, "the CQL regulariser (cql_alpha > 0) together with a target-policy table");
     if (v == e->cql_alpha) return DQNX_OK;
     e->cql_alpha = v;
     drop_graphs(e);   // alpha is a launch argument of the cached plans and picks the head kernels' instantiation
@@ -5839,6 +5957,234 @@ int dqnx_eval_chunk_timed(dqnx_engine* e, int64_t lo, void* scratch, uint64_t sc
     if (rc) return rc;
     if (kernel_index >= (int32_t)names.size()) return set_error(DQNX_EINVAL, "kernel index %d out of range", kernel_index);
     return eval_chunk(e, pl, lo, hi, 0, nullptr, s, kernel_index, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, nullptr);
+}
+
+// ---- fitted Q evaluation ------------------------------------------------------------------------------
+// Test hook: pi(s), pi(s') by fqe_argmax and one row through fqe_row, the serial forms of what k_policy_rows
+// and k_fqe_rows fold with 16 lanes.
+int dqnx_fqe_row(const float* raw_online, const float* raw_target_next, const float* raw_policy, const float* raw_policy_next,
+                 int32_t head, int32_t n_actions, int32_t action, float reward, float done, float gamma,
+                 dqnx_fqe_row_result* out) {
+    if (!raw_online || !raw_target_next || !raw_policy || !raw_policy_next || !out) return set_error(DQNX_EINVAL, "null argument");
+    if (head != DQNX_HEAD_LINEAR && head != DQNX_HEAD_DUELING) return set_error(DQNX_EINVAL, "fqe row: bad head kind");
+    const int maxa = head == DQNX_HEAD_DUELING ? 15 : 16;
+    if (n_actions < 1 || n_actions > maxa) return set_error(DQNX_EINVAL, "fqe row: need 1 <= n_actions <= %d", maxa);
+    float qp[16], qpn[16];
+    eval_q(raw_policy, head, n_actions, qp);
+    eval_q(raw_policy_next, head, n_actions, qpn);
+    const int ps = fqe_argmax(qp, n_actions), pn = fqe_argmax(qpn, n_actions);
+    const FqeRow r = fqe_row(raw_online, raw_target_next, head, n_actions, fqe_clamp(action, n_actions), reward, done, gamma, ps, pn);
+    memset(out, 0, sizeof(*out));
+    out->pi_s = ps;
+    out->pi_next = pn;
+    out->q_pi = r.qpi;
+    out->delta = r.delta;
+    out->huber = r.lb;
+    out->y = r.y;
+    return DQNX_OK;
+}
+
+int dqnx_policy_scratch_bytes(const dqnx_engine* e, uint64_t* bytes) { return dqnx_eval_scratch_bytes(e, bytes); }
+
+// the Double stream set on an engine planned for two streams: the MLP routes' workspace holds three streams
+// on every engine; the conv routes' column / activation buffers do too, but their split-K plans
+// (dense 1's slabs, the micro-CNN's samples per workgroup) were sized from the algorithm's stream count
+static bool policy_streams_ok(const dqnx_engine* e) { return e->cfg.algo != DQNX_ALGO_DQN || e->np.conv.empty(); }
+
+static int fqe_table_refused(const dqnx_engine* e, const int32_t* table, int64_t table_slots) {
+    if (!table) return set_error(DQNX_EINVAL, "null argument");
+    if (table_slots != e->cfg.capacity)
+        return set_error(DQNX_EINVAL, "policy table of %lld slots on an engine of capacity %lld", (long long)table_slots,
+                         (long long)e->cfg.capacity);
+    if (((uintptr_t)table) % 8) return set_error(DQNX_EINVAL, "policy table must be 8-byte aligned");
+    return DQNX_OK;
+}
+
+static FqePlan& fqe_plan_for(dqnx_engine* e, void* scratch) {
+    if (!e->fqe_plan || e->fqe_plan->scratch != scratch) e->fqe_plan = build_fqe_plan(e, scratch, policy_streams_ok(e));
+    return *e->fqe_plan;
+}
+
+// The launches of chunk c of [lo, hi) of the policy sweep (which = 0) or the value sweep (which = 1), in order;
+// timed / names as eval_chunk.
+static int fqe_chunk(dqnx_engine* e, FqePlan& pl, int which, int64_t lo, int64_t hi, int64_t c, int32_t* table,
+                     float* rows_out, hipStream_t s, int timed, hipEvent_t ev0, hipEvent_t ev1, std::vector<std::string>* names) {
+    const int64_t B = e->Bl, n = hi - lo, chunks = (n + B - 1) / B;
+    int k = 0, rc = DQNX_OK;
+    auto step = [&](const std::string& name, const std::function<int(hipStream_t)>& run) {
+        if (rc) return;
+        if (names) {
+            names->push_back(name);
+            return;
+        }
+        KernelTimer& kt = kernel_timer();
+        if (k == timed) {
+            kt.start = ev0;
+            kt.stop = ev1;
+        }
+        rc = run(s);
+        if (k == timed) {
+            if (!rc && kt.start) rc = set_error(DQNX_EUNSUPPORTED, "launch %d (%s) launches nothing through DQNX_LAUNCH", k, name.c_str());
+            kt.start = kt.stop = nullptr;
+        }
+        k++;
+    };
+    EvalIdxArgs ia = pl.ia;
+    ia.lo = lo;
+    ia.hi = hi;
+    ia.first = lo + c * B;
+    step("eval_idx", [&](hipStream_t cs) { return launch_eval_idx(ia, cs); });
+    for (const KStep& ks : which == 0 ? pl.fwd_pol : pl.fwd_val) {
+        if (c > 0 && timed < 0 && !names && ks.name == "conv_perm") continue;   // (as eval_chunk)
+        step(ks.name, ks.run);
+    }
+    const EvalHeadArgs& ha = which == 0 ? pl.ha_pol : pl.ha_val;
+    if (pl.head) step("eval_head", [&](hipStream_t cs) { return launch_eval_head(ha, cs); });
+    const int valid = (int)std::min<int64_t>(B, n - c * B);
+    if (which == 0) {
+        PolicyRowsArgs pa = pl.pa;
+        pa.valid = valid;
+        pa.table = table;
+        step("policy_rows", [&](hipStream_t cs) { return launch_policy_rows(pa, cs); });
+        return rc;
+    }
+    FqeRowsArgs ra = pl.ra;
+    ra.valid = valid;
+    ra.first = lo + c * B;
+    ra.table = table;
+    ra.rows_out = rows_out ? rows_out + c * B * 2 : nullptr;
+    step("fqe_rows", [&](hipStream_t cs) { return launch_fqe_rows(ra, cs); });
+    FqeFoldArgs fa = pl.fa;
+    fa.first = c == 0;
+    fa.last = c == chunks - 1;
+    fa.rows = n;
+    step("fqe_fold", [&](hipStream_t cs) { return launch_fqe_fold(fa, cs); });
+    return rc;
+}
+
+static int fqe_begin(dqnx_engine* e, int which, int64_t lo, int64_t hi, void* scratch, uint64_t scratch_bytes,
+                     const int32_t* table, int64_t table_slots, hipStream_t s) {
+    if (!e) return set_error(DQNX_EINVAL, "engine is null");
+    if (which != 0 && which != 1) return set_error(DQNX_EINVAL, "fqe: which must be 0 (policy sweep) or 1 (value sweep)");
+    // (before the bound check: these need no arena)
+    if (e->cfg.world_size > 1) return set_error(DQNX_EUNSUPPORTED, "fitted Q evaluation on a data-parallel engine (world_size > 1)");
+    int rc = fqe_table_refused(e, table, table_slots);
+    if (rc) return rc;
+    if (which == 0 && !policy_streams_ok(e))
+        return set_error(DQNX_EUNSUPPORTED, "policy sweep on a DQNAgent engine with conv layers: its conv plans are sized "
+                                            "for two streams, the sweep runs three");
+    return eval_begin(e, lo, hi, scratch, scratch_bytes, s);
+}
+
+int dqnx_policy_sweep(dqnx_engine* e, int64_t lo, int64_t hi, void* scratch, uint64_t scratch_bytes, int32_t* table,
+                      int64_t table_slots, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    int rc = fqe_begin(e, 0, lo, hi, scratch, scratch_bytes, table, table_slots, s);
+    if (rc) return rc;
+    FqePlan& pl = fqe_plan_for(e, scratch);
+    const int64_t B = e->Bl, chunks = (hi - lo + B - 1) / B;
+    for (int64_t c = 0; c < chunks; c++) {
+        rc = fqe_chunk(e, pl, 0, lo, hi, c, table, nullptr, s, -1, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+    }
+    DQNX_HIP_CHECK(hipStreamSynchronize(s));
+    return DQNX_OK;
+}
+
+int dqnx_fqe_range(dqnx_engine* e, int64_t lo, int64_t hi, void* scratch, uint64_t scratch_bytes, const int32_t* table,
+                   int64_t table_slots, float* rows_out, dqnx_fqe_result* result_out, void* stream) {
+    if (!result_out) return set_error(DQNX_EINVAL, "null argument");
+    if (((uintptr_t)rows_out) % 8) return set_error(DQNX_EINVAL, "fqe rows output must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    int rc = fqe_begin(e, 1, lo, hi, scratch, scratch_bytes, table, table_slots, s);
+    if (rc) return rc;
+    FqePlan& pl = fqe_plan_for(e, scratch);
+    const int64_t B = e->Bl, chunks = (hi - lo + B - 1) / B;
+    for (int64_t c = 0; c < chunks; c++) {
+        rc = fqe_chunk(e, pl, 1, lo, hi, c, const_cast<int32_t*>(table), rows_out, s, -1, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+    }
+    DQNX_HIP_CHECK(hipMemcpyAsync(result_out, pl.fa.acc, sizeof(dqnx_fqe_result), hipMemcpyDeviceToHost, s));
+    DQNX_HIP_CHECK(hipStreamSynchronize(s));
+    return DQNX_OK;
+}
+
+static int fqe_names(dqnx_engine* e, int32_t which, std::vector<std::string>& names) {
+    int rc = check_bound(e);
+    if (rc) return rc;
+    if (which != 0 && which != 1) return set_error(DQNX_EINVAL, "fqe: which must be 0 (policy sweep) or 1 (value sweep)");
+    if (which == 0 && !policy_streams_ok(e)) return set_error(DQNX_EUNSUPPORTED, "policy sweep on a DQNAgent engine with conv layers");
+    FqePlan& pl = fqe_plan_for(e, e->fqe_plan ? e->fqe_plan->scratch : nullptr);
+    return fqe_chunk(e, pl, which, 0, e->Bl, 0, nullptr, nullptr, nullptr, -1, nullptr, nullptr, &names);
+}
+
+int dqnx_fqe_kernel_count(dqnx_engine* e, int32_t which, int32_t* n) {
+    if (!n) return set_error(DQNX_EINVAL, "null argument");
+    std::vector<std::string> names;
+    int rc = fqe_names(e, which, names);
+    *n = (int32_t)names.size();
+    return rc;
+}
+
+int dqnx_fqe_kernel_name(dqnx_engine* e, int32_t which, int32_t index, char* name, int32_t name_len) {
+    if (!name || name_len < 1) return set_error(DQNX_EINVAL, "null argument");
+    std::vector<std::string> names;
+    int rc = fqe_names(e, which, names);
+    if (rc) return rc;
+    if (index < 0 || index >= (int32_t)names.size()) return set_error(DQNX_EINVAL, "kernel index %d out of range", index);
+    snprintf(name, (size_t)name_len, "%s", names[index].c_str());
+    return DQNX_OK;
+}
+
+int dqnx_fqe_chunk_timed(dqnx_engine* e, int32_t which, int64_t lo, void* scratch, uint64_t scratch_bytes, int32_t* table,
+                         int64_t table_slots, int32_t kernel_index, void* ev_start, void* ev_stop, void* stream) {
+    if (!e) return set_error(DQNX_EINVAL, "engine is null");
+    if (!ev_start || !ev_stop || kernel_index < 0) return set_error(DQNX_EINVAL, "null event or bad kernel index");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t hi = std::min<int64_t>(lo + e->Bl, e->ring_size);
+    int rc = fqe_begin(e, which, lo, hi, scratch, scratch_bytes, table, table_slots, s);
+    if (rc) return rc;
+    FqePlan& pl = fqe_plan_for(e, scratch);
+    std::vector<std::string> names;
+    rc = fqe_chunk(e, pl, which, lo, hi, 0, table, nullptr, s, -1, nullptr, nullptr, &names);
+    if (rc) return rc;
+    if (kernel_index >= (int32_t)names.size()) return set_error(DQNX_EINVAL, "kernel index %d out of range", kernel_index);
+    return fqe_chunk(e, pl, which, lo, hi, 0, table, nullptr, s, kernel_index, (hipEvent_t)ev_start, (hipEvent_t)ev_stop, nullptr);
+}
+
+static int tpol_refused(const dqnx_engine* e, double cql_alpha, bool table) {
+    if (!table) return DQNX_OK;
+    if (cql_alpha > 0.0)
+        return set_error(DQNX_EUNSUPPORTED, "a target-policy table together with the CQL regulariser (cql_alpha > 0)");
+    if (e->cfg.n_step > 1 || e->nstep)
+        return set_error(DQNX_EUNSUPPORTED, "a target-policy table on an n-step engine (n_step = %d): the uncorrected n-step "
+                                            "return would evaluate a mixture of the policy and the behaviour policy",
+                         (int)e->cfg.n_step);
+    if (e->cfg.world_size > 1) return set_error(DQNX_EUNSUPPORTED, "a target-policy table on a data-parallel engine (world_size > 1)");
+    return DQNX_OK;
+}
+
+int dqnx_set_target_policy(dqnx_engine* e, const int32_t* table, int64_t table_slots) {
+    if (!e) return set_error(DQNX_EINVAL, "engine is null");
+    int rc = state_pending(e, "set target policy");
+    if (rc) return rc;
+    if (table) {
+        rc = fqe_table_refused(e, table, table_slots);
+        if (rc) return rc;
+        rc = tpol_refused(e, e->cql_alpha, true);
+        if (rc) return rc;
+    }
+    if (table == e->tpol) return DQNX_OK;
+    e->tpol = table;
+    drop_graphs(e);   // the table is a launch argument of the cached plans and picks the head kernels' instantiation
+    return DQNX_OK;
+}
+
+int dqnx_get_target_policy(const dqnx_engine* e, const int32_t** table, int64_t* table_slots) {
+    if (!e || !table) return set_error(DQNX_EINVAL, "null argument");
+    *table = e->tpol;
+    if (table_slots) *table_slots = e->tpol ? e->cfg.capacity : 0;
+    return DQNX_OK;
 }
 
 int dqnx_nstep_buffer(const dqnx_engine* e, uint64_t* offset, uint64_t* bytes) {

@@ -727,7 +727,10 @@ constexpr int HB_SDH = 272;  // LDS row stride of bf16 dZ tiles (bf16 elements, 
 // CQL (dqnx_set_cql, alpha > 0): the conservative regulariser a.cql_alpha * (logsumexp_j Q(s, j) - Q(s, a)) joins
 // the row's loss and gradient (cql.hpp): three more 16-lane butterflies (max, sum of exp, sum of dq), one expf
 // and one logf per lane.  A template parameter for the same reason.
-template <int ACT, int NL, bool BF, bool DISC, bool CQL>
+// TPOL (dqnx_set_target_policy): q' = Q_target(s', a.tpol[phys[b]][1]), a fixed property of the row's ring slot,
+// instead of the max / the online argmax (fitted Q evaluation; the step then runs no online(s') stream).  Only
+// instantiated with DISC = false, CQL = false; a template parameter for the same reason again.
+template <int ACT, int NL, bool BF, bool DISC, bool CQL, bool TPOL>
 __global__ __launch_bounds__(FT) void k_head_bwd(HeadBwdArgs a) {
     __shared__ __attribute__((aligned(16))) float dzs[2][16 * HB_SD];
     __shared__ float dh[16][17];
@@ -737,10 +740,16 @@ __global__ __launch_bounds__(FT) void k_head_bwd(HeadBwdArgs a) {
     // nsplit workgroups per 16-sample tile: each recomputes the (cheap) head part and takes
     // 1/nsplit of the columns of the LAST dZ of the chain (dZ_1, the widest)
     // every argument the tile mapping and the prologue loads read: one wait (DQNX_KERNARG, common.hpp)
-    asm volatile("" ::DQNX_KERNARG(a.nsplit), DQNX_KERNARG(a.xcd_rows), DQNX_KERNARG(a.xcd_shift), DQNX_KERNARG(a.xcd_mr),
-                 DQNX_KERNARG(a.Bl), DQNX_KERNARG(a.NH), DQNX_KERNARG(a.F), DQNX_KERNARG(a.head_kind), DQNX_KERNARG(a.params),
-                 DQNX_KERNARG(a.head_off), DQNX_KERNARG(a.raw), DQNX_KERNARG(a.trans), DQNX_KERNARG(a.isw),
-                 DQNX_KERNARG(a.H[NL - 1]));
+    if constexpr (TPOL)
+        asm volatile("" ::DQNX_KERNARG(a.nsplit), DQNX_KERNARG(a.xcd_rows), DQNX_KERNARG(a.xcd_shift), DQNX_KERNARG(a.xcd_mr),
+                     DQNX_KERNARG(a.Bl), DQNX_KERNARG(a.NH), DQNX_KERNARG(a.F), DQNX_KERNARG(a.head_kind), DQNX_KERNARG(a.params),
+                     DQNX_KERNARG(a.head_off), DQNX_KERNARG(a.raw), DQNX_KERNARG(a.trans), DQNX_KERNARG(a.isw),
+                     DQNX_KERNARG(a.H[NL - 1]), DQNX_KERNARG(a.phys), DQNX_KERNARG(a.tpol), DQNX_KERNARG(a.tpol_slots));
+    else
+        asm volatile("" ::DQNX_KERNARG(a.nsplit), DQNX_KERNARG(a.xcd_rows), DQNX_KERNARG(a.xcd_shift), DQNX_KERNARG(a.xcd_mr),
+                     DQNX_KERNARG(a.Bl), DQNX_KERNARG(a.NH), DQNX_KERNARG(a.F), DQNX_KERNARG(a.head_kind), DQNX_KERNARG(a.params),
+                     DQNX_KERNARG(a.head_off), DQNX_KERNARG(a.raw), DQNX_KERNARG(a.trans), DQNX_KERNARG(a.isw),
+                     DQNX_KERNARG(a.H[NL - 1]));
     // nsplit and xcd_mr are 1, 2 or 4 (launch_head_bwd checks): shifts, not runtime divisions
     const int nsh = __builtin_ctz(a.nsplit), msh = __builtin_ctz(a.xcd_mr);
     int tile = (int)(blockIdx.x >> nsh), part = blockIdx.x - (tile << nsh);
@@ -786,8 +795,14 @@ __global__ __launch_bounds__(FT) void k_head_bwd(HeadBwdArgs a) {
     const int hbc = hb < nb ? hb : nb - 1;
     float r0 = 0.f, r1 = 0.f, r2 = 0.f, wis = 1.f, gm = 0.f;
     float4 tr = make_float4(0.f, 0.f, 0.f, 0.f);
+    int ap = 0;   // TPOL: the row's table entry pi(s')
     if (tid < 256) {
         const int64_t base = (int64_t)(b0 + hbc) * 16 + hj;
+        if constexpr (TPOL) {   // (the one dependent trip: first)
+            const int64_t slot = a.phys[b0 + hbc];
+            const bool in = slot >= 0 && slot < a.tpol_slots;
+            ap = in ? a.tpol[slot * 2 + 1] : -1;   // (outside the caller's table: nothing is read; reported below)
+        }
         r0 = a.raw[base];
         r1 = a.raw[(int64_t)a.Bl * 16 + base];   // online(s') (Double) / unused (DQN)
         r2 = a.raw[(int64_t)2 * a.Bl * 16 + base];
@@ -828,7 +843,14 @@ __global__ __launch_bounds__(FT) void k_head_bwd(HeadBwdArgs a) {
         };
         const float q0 = qval(r0), q1 = qval(r1), q2 = qval(r2);
         float qn;
-        if (!use1) {   // target(s').max(1)
+        if constexpr (TPOL) {   // target(s') at the table's action; an entry outside [0, A): the error word, action 0
+            if (ap < 0 || ap >= A) {
+                if (hj == 0 && hb < nb && a.err)
+                    __hip_atomic_store(a.err, (int32_t)DQNX_DEVERR_TPOL_ACTION, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ap = 0;
+            }
+            qn = __shfl(q2, ap, 16);
+        } else if (!use1) {   // target(s').max(1)
             float mx = hj < A ? q2 : -INFINITY;
 #pragma unroll
             for (int m = 8; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 16));
@@ -1551,24 +1573,30 @@ int launch_head_bwd(const HeadBwdArgs& a, int act, hipStream_t s) {
     if (!pow2_le4(a.nsplit) || !pow2_le4(a.xcd_mr))   // (the kernel divides by them with shifts)
         return set_error(DQNX_EINVAL, "fused head: nsplit %d / row-tile height %d must be 1, 2 or 4", a.nsplit, a.xcd_mr);
     const size_t pad = DQNX_HEAD_LDS_PAD;   // dynamic LDS on top of the static tiles (occupancy knob)
-#define HEAD_BWD_LAUNCH2(ACTV, NLV, BFV, DV, CV)                                                     \
+#define HEAD_BWD_LAUNCH2(ACTV, NLV, BFV, DV, CV, TV)                                                 \
     do {                                                                                             \
-        if (pad > 64 * 1024) allow_lds(k_head_bwd<ACTV, NLV, BFV, DV, CV>, 120 * 1024);              \
-        DQNX_LAUNCH((k_head_bwd<ACTV, NLV, BFV, DV, CV>), grid, block, pad, s, a);                   \
+        if (pad > 64 * 1024) allow_lds(k_head_bwd<ACTV, NLV, BFV, DV, CV, TV>, 120 * 1024);          \
+        DQNX_LAUNCH((k_head_bwd<ACTV, NLV, BFV, DV, CV, TV>), grid, block, pad, s, a);               \
     } while (0)
     const bool cql = a.cql_alpha > 0.f;   // the one place this kernel's CQL instantiation is picked
+    // ... and its TPOL instantiation (only with DISC = false, CQL = false: the engine refuses the combinations)
+    const bool tpol = a.tpol != nullptr;
+    if (tpol && (cql || a.disc || !a.phys))
+        return set_error(DQNX_EUNSUPPORTED, "fused head: a target-policy table with CQL, n-step rows or no slot table");
 #define HEAD_BWD_LAUNCH(ACTV, NLV, BFV, DV)                                                          \
     do {                                                                                             \
-        if (cql) HEAD_BWD_LAUNCH2(ACTV, NLV, BFV, DV, true);                                         \
-        else HEAD_BWD_LAUNCH2(ACTV, NLV, BFV, DV, false);                                            \
+        if (cql) HEAD_BWD_LAUNCH2(ACTV, NLV, BFV, DV, true, false);                                  \
+        else HEAD_BWD_LAUNCH2(ACTV, NLV, BFV, DV, false, false);                                     \
     } while (0)
 #define HEAD_BWD_CASE(ACTV, NLV)                                                                     \
     do {                                                                                             \
         if (a.bf16) {                                                                                \
-            if (a.disc) HEAD_BWD_LAUNCH(ACTV, NLV, true, true);                                      \
+            if (tpol) HEAD_BWD_LAUNCH2(ACTV, NLV, true, false, false, true);                         \
+            else if (a.disc) HEAD_BWD_LAUNCH(ACTV, NLV, true, true);                                 \
             else HEAD_BWD_LAUNCH(ACTV, NLV, true, false);                                            \
         } else {                                                                                     \
-            if (a.disc) HEAD_BWD_LAUNCH(ACTV, NLV, false, true);                                     \
+            if (tpol) HEAD_BWD_LAUNCH2(ACTV, NLV, false, false, false, true);                        \
+            else if (a.disc) HEAD_BWD_LAUNCH(ACTV, NLV, false, true);                                \
             else HEAD_BWD_LAUNCH(ACTV, NLV, false, false);                                           \
         }                                                                                            \
     } while (0)

@@ -407,7 +407,9 @@ __global__ __launch_bounds__(256) void k_bwd_level(BwdArgs a) {
 // a.gamma (a template parameter: the default engine's kernel is the code it was).
 // CQL (dqnx_set_cql, alpha > 0): thread (b, 0) also folds the row's conservative regulariser through cql_row
 // (cql.hpp) into the LDS row cqs[b] = p_j - [j == a]; step (4) forms dq_j from it.  A template parameter too.
-template <int ACT, int F, bool DISC, bool CQL>
+// TPOL (dqnx_set_target_policy): thread (b, 0) takes q' = Q_target(s', a.tpol[phys[b]][1]) instead of the max /
+// the online argmax (fitted Q evaluation).  Only instantiated with DISC = false, CQL = false.
+template <int ACT, int F, bool DISC, bool CQL, bool TPOL>
 __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
     constexpr int TS = 16, QS = 17;
     constexpr int SF = F + 8, F4 = F / 4;
@@ -461,10 +463,14 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
         }
         if (tid < TS) {
             const int b = tid;
-            int act = 0;
+            int act = 0, ap = 0;
             float rew = 0.f, done = 0.f, w = 1.f, gm = a.gamma;
             if (b < nb) {
                 const int slot = a.phys[b0 + b];
+                if constexpr (TPOL) {   // (with the row's other slot loads; a slot outside the caller's table: nothing is read; reported)
+                    const bool in = slot >= 0 && slot < a.tpol_slots;
+                    ap = in ? a.tpol[(int64_t)slot * 2 + 1] : -1;
+                }
                 act = a.act[slot];
                 rew = a.rew[slot];
                 done = a.done[slot];
@@ -477,6 +483,7 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
             dsh[b] = done;
             wsh[b] = w;
             if constexpr (DISC) gmsh[b] = gm;
+            if constexpr (TPOL) gmsh[b] = __int_as_float(ap);   // (gmsh is DISC's, never live with TPOL)
         }
     }
     __syncthreads();
@@ -530,7 +537,16 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
         float gq = 0.f, lb = 0.f;
         if (b < nb) {
             float qn;
-            if (!use1) {                                   // target(s').max(1) (R:dqn/agent.py:172-173)
+            if constexpr (TPOL) {                          // target(s') at the table's action
+                int ap = __float_as_int(gmsh[b]);
+                if (ap < 0 || ap >= A) {                   // the sticky error word; the row goes on with action 0
+                    if (a.ctrl)
+                        __hip_atomic_store(&a.ctrl->error, (int32_t)DQNX_DEVERR_TPOL_ACTION, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+                    ap = 0;
+                }
+                qn = qv[2][b][ap];
+            } else if (!use1) {                            // target(s').max(1) (R:dqn/agent.py:172-173)
                 qn = qv[2][b][0];
                 for (int j = 1; j < A; j++) qn = qv[2][b][j] > qn ? qv[2][b][j] : qn;
             } else {                                       // argmax online(s'), gather target(s') (:210-214)
@@ -1624,9 +1640,14 @@ static void launch_head_f(const HeadArgs& a, int act, int tiles, hipStream_t s) 
     const bool cql = a.cql_alpha > 0.f;   // the one place this kernel's CQL instantiation is picked
 #define HEAD_LAUNCH(ACTV, DV)                                                                       \
     do {                                                                                            \
-        if (cql) DQNX_LAUNCH((k_head<ACTV, F, DV, true>), dim3(tiles), dim3(256), 0, s, a);          \
-        else DQNX_LAUNCH((k_head<ACTV, F, DV, false>), dim3(tiles), dim3(256), 0, s, a);             \
+        if (cql) DQNX_LAUNCH((k_head<ACTV, F, DV, true, false>), dim3(tiles), dim3(256), 0, s, a);   \
+        else DQNX_LAUNCH((k_head<ACTV, F, DV, false, false>), dim3(tiles), dim3(256), 0, s, a);      \
     } while (0)
+    if (a.tpol) {   // ... and its TPOL instantiation (launch_head refused it with CQL or n-step rows)
+        if (act == DQNX_ACT_RELU) DQNX_LAUNCH((k_head<DQNX_ACT_RELU, F, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
+        else DQNX_LAUNCH((k_head<DQNX_ACT_ELU, F, false, false, true>), dim3(tiles), dim3(256), 0, s, a);
+        return;
+    }
     if (a.disc) {
         if (act == DQNX_ACT_RELU) HEAD_LAUNCH(DQNX_ACT_RELU, true);
         else HEAD_LAUNCH(DQNX_ACT_ELU, true);
@@ -1641,6 +1662,8 @@ bool head_supported(int F) { return F == 64 || F == 128 || F == 256; }
 
 int launch_head(const HeadArgs& a, int act, hipStream_t s) {
     const int tiles = (a.Bl + 15) / 16;
+    if (a.tpol && (a.cql_alpha > 0.f || a.disc))
+        return set_error(DQNX_EUNSUPPORTED, "head: a target-policy table with CQL or n-step rows");
     switch (a.F) {
         case 64: launch_head_f<64>(a, act, tiles, s); break;
         case 128: launch_head_f<128>(a, act, tiles, s); break;

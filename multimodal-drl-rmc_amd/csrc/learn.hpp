@@ -180,6 +180,11 @@ struct HeadArgs {
     // fp32(alpha) of the conservative regulariser (dqnx_set_cql): > 0 picks k_head<.., CQL = true>; 0: off, the
     // kernel of an engine that never set it.  After disc, for the same reason.
     float cql_alpha;
+    // the target-policy table int32 [capacity][2] by ring slot (dqnx_set_target_policy): non-null picks
+    // k_head<.., TPOL = true>, q' = Q_target(s', tpol[phys[b]][1]); an entry outside [0, A), or a slot outside
+    // [0, tpol_slots) (the table is the caller's, outside the arena: nothing is read), sets ctrl.error
+    const int32_t* tpol;
+    int64_t tpol_slots;
 };
 
 constexpr int kMaxSeg = 10;
@@ -603,6 +608,13 @@ struct HeadBwdArgs {
     // fp32(alpha) of the conservative regulariser (dqnx_set_cql): > 0 picks k_head_bwd<.., CQL = true>; 0: off,
     // the kernel of an engine that never set it.  After disc, for the same reason.
     float cql_alpha;
+    // the target-policy table int32 [capacity][2] by ring slot (dqnx_set_target_policy): non-null picks
+    // k_head_bwd<.., TPOL = true>, q' = Q_target(s', tpol[phys[b]][1]); an entry outside [0, A) of a real row
+    // -- or a slot outside [0, tpol_slots): the table is the caller's, outside the arena, so nothing is
+    // read -- stores DQNX_DEVERR_TPOL_ACTION to err (&ctrl.error: this kernel's own ctrl is null on the fused plan)
+    const int32_t* tpol;
+    int64_t tpol_slots;
+    int32_t* err;
 };
 bool fused_fwd_plan(FusedFwdArgs& a, int obs_dim, bool bf16, int mr);   // fills sx/sh/buf/kpad; false if unsupported
 int fused_wblk_bytes(bool bf16, int rows, int kpad);          // one blocked weight copy

@@ -131,6 +131,22 @@ class EvalRowResult(ctypes.Structure):
                 ("action_gap", ctypes.c_float), ("y", ctypes.c_float), ("reserved0", ctypes.c_float)]
 
 
+# fitted Q evaluation (dqnx.h "fitted Q evaluation")
+DEVERR_TPOL_ACTION = 20
+
+
+class FqeResult(ctypes.Structure):
+    _fields_ = [("rows", I64), ("start_rows", I64), ("q_pi_sum", ctypes.c_double), ("q_pi_start_sum", ctypes.c_double),
+                ("abs_td_sum", ctypes.c_double), ("huber_sum", ctypes.c_double), ("q_pi_max", ctypes.c_double),
+                ("q_pi_min", ctypes.c_double)]
+
+
+class FqeRowResult(ctypes.Structure):
+    _fields_ = [("pi_s", I32), ("pi_next", I32), ("q_pi", ctypes.c_float), ("delta", ctypes.c_float),
+                ("huber", ctypes.c_float), ("y", ctypes.c_float), ("reserved0", ctypes.c_float),
+                ("reserved1", ctypes.c_float)]
+
+
 # training-state snapshot (dqnx.h "training-state snapshot")
 STATE_MAGIC = 0x54415453584E5144   # b"DQNXSTAT" little-endian
 STATE_VERSION = 1
@@ -178,6 +194,8 @@ EXPORTS = [
     "dqnx_set_cql", "dqnx_get_cql", "dqnx_cql_row",
     "dqnx_eval_scratch_bytes", "dqnx_eval_range", "dqnx_eval_row", "dqnx_eval_kernel_count",
     "dqnx_eval_kernel_name", "dqnx_eval_chunk_timed",
+    "dqnx_policy_scratch_bytes", "dqnx_policy_sweep", "dqnx_set_target_policy", "dqnx_get_target_policy",
+    "dqnx_fqe_range", "dqnx_fqe_row", "dqnx_fqe_kernel_count", "dqnx_fqe_kernel_name", "dqnx_fqe_chunk_timed",
 ]
 
 GIL_HELD = ("dqnx_agent_learn_mt", "dqnx_agent_choose")   # entry points called with the GIL held (see lib())
@@ -279,6 +297,16 @@ def lib():
         "dqnx_eval_kernel_count": ([vp, P(I32)], ctypes.c_int),
         "dqnx_eval_kernel_name": ([vp, I32, ctypes.c_char_p, I32], ctypes.c_int),
         "dqnx_eval_chunk_timed": ([vp, I64, vp, ctypes.c_uint64, I32, vp, vp, vp], ctypes.c_int),
+        "dqnx_policy_scratch_bytes": ([vp, P(ctypes.c_uint64)], ctypes.c_int),
+        "dqnx_policy_sweep": ([vp, I64, I64, vp, ctypes.c_uint64, vp, I64, vp], ctypes.c_int),
+        "dqnx_set_target_policy": ([vp, vp, I64], ctypes.c_int),
+        "dqnx_get_target_policy": ([vp, P(vp), P(I64)], ctypes.c_int),
+        "dqnx_fqe_range": ([vp, I64, I64, vp, ctypes.c_uint64, vp, I64, vp, P(FqeResult), vp], ctypes.c_int),
+        "dqnx_fqe_row": ([P(ctypes.c_float), P(ctypes.c_float), P(ctypes.c_float), P(ctypes.c_float), I32, I32, I32,
+                          ctypes.c_float, ctypes.c_float, ctypes.c_float, P(FqeRowResult)], ctypes.c_int),
+        "dqnx_fqe_kernel_count": ([vp, I32, P(I32)], ctypes.c_int),
+        "dqnx_fqe_kernel_name": ([vp, I32, I32, ctypes.c_char_p, I32], ctypes.c_int),
+        "dqnx_fqe_chunk_timed": ([vp, I32, I64, vp, ctypes.c_uint64, vp, I64, I32, vp, vp, vp], ctypes.c_int),
         "dqnx_nstep_window": ([vp, vp, I64, I64, I32, I32, ctypes.c_double, P(ctypes.c_float), P(ctypes.c_float),
                                P(ctypes.c_float), P(I64), P(I32)], ctypes.c_int),
     }

@@ -297,6 +297,7 @@ class LearnEngine:
         self.collect_stats = False
         self.grad_clip = 0.0
         self.cql_alpha = 0.0
+        self._tpol = None        # the table set_target_policy holds a reference to
         self._stepped = False    # a learn step of this engine has filled q / td (cql_gap)
         self.ring_size = 0
         self.ring_wptr = 0
@@ -765,6 +766,70 @@ class LearnEngine:
              "greedy_hist": [int(x) for x in st.greedy_hist[:A]], "taken_hist": [int(x) for x in st.taken_hist[:A]]}
         return (d, per_row) if rows else d
 
+    # ---- fitted Q evaluation (dqnx_policy_sweep / _set_target_policy / _fqe_range: include/dqnx.h) ----
+    def policy_actions(self, lo=0, hi=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The policy-action table of the engine's ONLINE network over the replay rows [lo, hi) (logical
+        positions; hi = None: the ring's size): int32 [capacity, 2] by PHYSICAL ring slot, [slot, 0] = argmax_a
+        Q(obs[slot], a), [slot, 1] = argmax_a Q(next_obs[slot], a), first maximum.  out: a table to fill (slots
+        outside the range keep what they held); else a new one whose other slots are -1.  Nothing of the
+        training state changes."""
+        self.launch_recorded()
+        hi = self.ring_size if hi is None else int(hi)
+        if out is None:
+            out = torch.full((self.capacity, 2), -1, dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 2
+        sc = self.eval_scratch()
+        C.check(self.L.dqnx_policy_sweep(self.h, int(lo), hi, ctypes.c_void_p(sc.data_ptr()), sc.numel(),
+                                         ctypes.c_void_p(out.data_ptr()), int(out.shape[0]), self.stream()), "policy_sweep")
+        return out
+
+    def set_target_policy(self, table: Optional[torch.Tensor]) -> None:
+        """With a policy-action table (policy_actions) every following learn step regresses on
+        y = r + (1 - d) * gamma * Q_target(s', table[slot, 1]) -- fitted Q evaluation of that policy -- and runs
+        the online(s), target(s') streams only.  None restores the engine's own target rule.  The engine keeps a
+        reference to the tensor; push and load_state are refused while a table is set."""
+        self.settle()
+        if table is None:
+            C.check(self.L.dqnx_set_target_policy(self.h, None, 0), "set_target_policy")
+            self._tpol = None
+            return
+        assert table.dtype == torch.int32 and table.is_contiguous() and table.dim() == 2 and table.shape[1] == 2
+        C.check(self.L.dqnx_set_target_policy(self.h, ctypes.c_void_p(table.data_ptr()), int(table.shape[0])),
+                "set_target_policy")
+        self._tpol = table
+
+    def fqe_value_raw(self, table: torch.Tensor, lo=0, hi=None, rows_out: Optional[torch.Tensor] = None) -> C.FqeResult:
+        assert table.dtype == torch.int32 and table.is_contiguous() and table.dim() == 2 and table.shape[1] == 2
+        assert rows_out is None or (rows_out.dtype == torch.float32 and rows_out.is_contiguous())
+        self.launch_recorded()
+        hi = self.ring_size if hi is None else int(hi)
+        sc = self.eval_scratch()
+        out = C.FqeResult()
+        rp = ctypes.c_void_p(rows_out.data_ptr()) if rows_out is not None else None
+        C.check(self.L.dqnx_fqe_range(self.h, int(lo), hi, ctypes.c_void_p(sc.data_ptr()), sc.numel(),
+                                      ctypes.c_void_p(table.data_ptr()), int(table.shape[0]), rp, ctypes.byref(out),
+                                      self.stream()), "fqe_range")
+        return out
+
+    def fqe_value(self, table: torch.Tensor, lo=0, hi=None, rows=False):
+        """The fitted-Q-evaluation estimate of the table's policy under the engine's weights over the replay rows
+        [lo, hi): a dict -- rows, start_rows (episode starts: the oldest n_env rows and every row after a done
+        of its environment), value (mean Q(s0, pi(s0)) over start rows: the estimate of the policy's discounted
+        return; None without a start row), q_pi_mean / q_pi_max / q_pi_min over all rows, abs_td_mean and loss
+        (|delta| and unweighted Huber of r + (1 - d) * gamma * Q_target(s', pi(s')) - Q(s, a)).  ONE blocking
+        read; nothing of the training state changes.  rows=True: (dict, tensor [hi - lo, 2] of (q_pi, delta))."""
+        hi = self.ring_size if hi is None else int(hi)
+        per_row = None
+        if rows:
+            per_row = torch.empty((max(hi - int(lo), 0), 2), dtype=torch.float32, device=self.device)
+        st = self.fqe_value_raw(table, lo, hi, per_row)
+        n = max(int(st.rows), 1)
+        d = {"rows": int(st.rows), "start_rows": int(st.start_rows),
+             "value": st.q_pi_start_sum / int(st.start_rows) if st.start_rows else None,
+             "q_pi_mean": st.q_pi_sum / n, "q_pi_max": float(st.q_pi_max), "q_pi_min": float(st.q_pi_min),
+             "abs_td_mean": st.abs_td_sum / n, "loss": st.huber_sum / n}
+        return (d, per_row) if rows else d
+
     def grad_clip_info(self, reset=False) -> dict:
         """What the clipped steps since the last reset saw: ONE blocking read, meant for log cadence.
         steps, clipped_steps (coef < 1), norm_sum / norm_max / last_norm (the PRE-clip global norm),
@@ -886,6 +951,9 @@ def raise_device_error(err: int):
         raise RuntimeError("libdqnx: paired-column forward hand-off timed out inside a launch (internal error)")
     if err == C.DEVERR_NSTEP_STATE:
         raise RuntimeError("libdqnx: the n-step gather met a ring size, write pointer or sampled slot outside the ring")
+    if err == C.DEVERR_TPOL_ACTION:
+        raise RuntimeError("libdqnx: a sampled row's target-policy table entry lies outside [0, n_actions) "
+                           "(set_target_policy; the row was computed with action 0)")
     if err in C.DEVERR_BOUNDS:
         raise RuntimeError(f"libdqnx: out-of-range write skipped (internal error): {C.DEVERR_BOUNDS[err]}")
     if err:

@@ -15,6 +15,13 @@ training and a held-out engine from one saved ring, and fit(validate=...) report
 
     train, val = offline.split("run.dqnx", holdout=20000, batch=1024, cql_alpha=1.0)
     log = offline.fit(train, 20000, log_every=1000, validate=val, validate_every=1000)
+
+What evaluate() reports are properties of the Q function.  fqe() estimates the discounted return of a candidate
+POLICY from the logged transitions alone (fitted Q evaluation, include/dqnx.h "fitted Q evaluation"): the
+policy's actions are computed once per ring slot, a fresh network is fitted to r + gamma * Q_target(s', pi(s')),
+and the mean of Q(s0, pi(s0)) over episode-start states is the estimate.
+
+    est = offline.fqe(candidate_engine, "run.dqnx", 5000, batch=1024, lr=3e-4)["value"]
 """
 import ctypes
 from typing import List, Optional
@@ -156,4 +163,68 @@ def fit(engine: LearnEngine, steps: int, soft_update: bool = True, log_every: in
             out[-1].update({"val_loss": ev["loss"], "val_cql_gap": ev["cql_gap"], "val_agree": ev["agree"],
                             "val_q_sa_mean": ev["q_sa_mean"], "val_v_mean": ev["v_mean"],
                             "val_abs_td_mean": ev["abs_td_mean"]})
+    return out
+
+
+def fresh_params(engine: LearnEngine, seed: int) -> dict:
+    """name -> tensor: a fresh parameter set for the engine's network from `seed`, by torch's default rule for
+    Linear / Conv2d (weights and biases uniform in +-1 / sqrt(fan_in)), drawn from a CPU generator in
+    state_dict order."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(int(seed))
+    out, fan_in = {}, 1
+    for name, _, shape in engine.param_layout:
+        if len(shape) >= 2:
+            fan_in = int(np.prod(shape[1:]))
+        bound = 1.0 / float(max(fan_in, 1)) ** 0.5
+        out[name] = (torch.rand(tuple(shape), generator=g, dtype=torch.float32) * 2.0 - 1.0) * bound
+    return out
+
+
+def fresh_fit_state(engine: LearnEngine, seed: int) -> None:
+    """Both networks := fresh_params(engine, seed); the Adam moments and step count start from zero.  The ring,
+    the RNG states and (prioritised engines) the priorities stay."""
+    engine.launch_recorded()
+    engine.load_params(fresh_params(engine, seed))
+    engine.adam_m.zero_()
+    engine.adam_v.zero_()
+    off = C.Ctrl.adam_step.offset
+    engine.ctrl_bytes[off:off + 8].zero_()
+
+
+def fqe(policy, data, steps: int, soft_update: bool = True, seed: int = 0, log_every: int = 0, **engine_kw) -> dict:
+    """Fitted Q evaluation of `policy` on the transitions of `data`.
+    policy: a LearnEngine (its online network) or a state_dict-like name -> tensor of the data's network.
+    data: a training-state blob (a path, a file object, bytes, a uint8 array) or a LearnEngine (its state_blob()).
+    A data engine is built with engine_from_state(data, **engine_kw) (batch, lr, gamma, tau, algo, ...); the policy
+    goes into its online parameters and policy_actions() sweeps the whole ring once; then both networks are
+    re-initialised from `seed` (fresh_fit_state), the table is set as the target policy and fit() runs `steps`
+    learn steps.  Returns fqe_value()'s dict over the whole ring -- "value" is the estimate of the policy's
+    discounted return from the episode starts -- plus "log" (fit's records) and "steps".  `policy` and a `data`
+    engine are not changed.
+    A prioritised blob gives a prioritised engine by default: the fit then samples by the blob's priorities
+    (updated by the fit's own |delta|), which weights the regression towards high-priority rows and changes what
+    "value" estimates.  A prioritised blob needs a prioritised algorithm (engine_from_state), so for the estimate
+    under uniform sampling push ring_rows() of the prioritised engine into a uniform LearnEngine and pass that
+    engine as `data`."""
+    blob = data.state_blob() if isinstance(data, LearnEngine) else _read_blob(data)
+    eng = engine_from_state(blob, **engine_kw)
+    if isinstance(policy, LearnEngine):
+        policy.launch_recorded()
+        eng.params.copy_(policy.params)
+        eng.params_modified()
+    else:
+        eng.load_params(policy)
+    table = eng.policy_actions()
+    fresh_fit_state(eng, seed)
+    eng.set_target_policy(table)
+    try:
+        log = fit(eng, steps, soft_update=soft_update, log_every=log_every)
+        torch.cuda.synchronize(eng.device)
+        eng.check_device_error()
+        out = eng.fqe_value(table)
+    finally:
+        eng.set_target_policy(None)
+    out["log"] = log
+    out["steps"] = int(steps)
     return out
